@@ -1,7 +1,13 @@
 """DGVCC MI355X benchmark: train-step frames/s at 768x1024 (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode final|simple|base]
-                    [--precision fp32|bf16] [--no-bf16] [--trunk ibn|sw|isw]
+                    [--precision fp32|bf16] [--no-bf16] [--trunk ibn|sw|isw] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps of the headline leg, writes that leg's outputs when
+`--dump-outputs DIR` is given (dump_outputs) and prints the result line with the leg's `roofline`
+(HIP events around the conv launches of the timed steps themselves).  `--full` adds everything that takes
+runs of its own: the `f32_exact` and `perf_bf16` legs, `dmap`, `bl`, `cpu_baseline` with the full-frame
+parity, and `params_in_sync` for several ranks.
 
 Default workload = the config BASELINE.json's metric is quoted on, configs/sta_final.yml
 (ShanghaiTech-A "final"): DGModel_final, DGTrainer 'final' mode (two photometric views,
@@ -29,7 +35,7 @@ optimizer, max-over-ranks timing.
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the implicit-GEMM conv
 forward/dgrad launches, each timed with HIP events on its launch stream over the timed
 region; `traffic` = PMC HBM bytes per launch of the same workload from profiles/traffic/,
-null when that workload has not been profiled) and `cpu_baseline` (the oracle's CPU
+null when that workload has not been profiled) and, with `--full`, `cpu_baseline` (the oracle's CPU
 restatement of the same step on a bounded sample on this host's cores, plus the full-frame
 fp32 parity of the HIP path against it).
 """
@@ -39,8 +45,10 @@ import argparse
 import json
 import os
 import socket
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 
 import torch
@@ -100,6 +108,13 @@ def parse():
     ap.add_argument("--width", type=int, default=W0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg also run everything else the benchmark measures or checks: the "
+                         "f32_exact and perf_bf16 legs, the dmap and BL timings, the CPU baseline with its full-frame "
+                         "parity, and the multi-rank params_in_sync check (each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed train step left with its caller to "
+                         "DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank plumbing (launcher, gloo ranks, per-rank timing "
                          "aggregation and the JSON line) with a toy step instead of the GPU workload")
@@ -275,9 +290,40 @@ FWD_KERNEL_NAMES = {
 }
 
 
-def run_leg(args, precision, dev, world, rank):
+def dump_outputs(path, model, last_loss, cap=4_000_000):
+    """`--dump-outputs DIR`: what the last timed DGTrainer.train_step left with its caller, as float
+    arrays under DIR: `loss.npy` (float64 [1]: the step's return value), `state.npy` (float32: the
+    model's parameters, then its floating-point buffers, after the step's update) and `grads.npy`
+    (float32: each parameter's .grad, zeros where it has none).  state / grads are the tensors
+    flattened and concatenated in named_parameters() / named_buffers() order; a tensor with more than
+    `cap // tensors` elements (at most 16384) contributes that many elements at indices drawn from a
+    generator seeded by the tensor's position, the same in every run and for both files: at most
+    4 x cap bytes per file (32 MB in all at the default)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    bufs = [b for _, b in model.named_buffers() if b.is_floating_point()]
+    k = max(1, min(16384, cap // max(1, len(params) + len(bufs))))
+
+    def sample(i, t):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > k:
+            g = torch.Generator(device="cpu").manual_seed(7919 + i)
+            flat = flat[torch.randint(flat.numel(), (k,), generator=g).to(flat.device)]
+        return flat.float().cpu()
+
+    state = torch.cat([sample(i, t) for i, t in enumerate(params + bufs)])
+    grads = torch.cat([sample(i, p.grad if p.grad is not None else torch.zeros_like(p))
+                       for i, p in enumerate(params)])
+    np.save(os.path.join(path, "loss.npy"), np.asarray([last_loss], dtype=np.float64))
+    np.save(os.path.join(path, "state.npy"), state.numpy())
+    np.save(os.path.join(path, "grads.npy"), grads.numpy())
+
+
+def run_leg(args, precision, dev, world, rank, dump_dir=None):
     """Build, warm up and time one precision of the workload; returns the measurements.
-    precision "fp32_exact" = fp32 with the conv GEMMs on v_mfma_f32_16x16x4_f32."""
+    precision "fp32_exact" = fp32 with the conv GEMMs on v_mfma_f32_16x16x4_f32.  dump_dir: rank 0
+    writes the last timed step's outputs there (dump_outputs), outside the timed region."""
     from dgvcc_amd import kernels as K
     K.call("dg_set_f32_math", 0 if precision == "fp32_exact" else F32_MATH_MODE[args.f32_math])
     precision = "fp32" if precision == "fp32_exact" else precision
@@ -298,8 +344,8 @@ def run_leg(args, precision, dev, world, rank):
     dp = {"overlap": opt.reducer is not None,
           "bucket_mb": round(opt.reducer.bucket_bytes / (1 << 20), 3) if opt.reducer is not None else None}
     cwd = os.getcwd()
-    os.makedirs("/tmp/dgvcc_bench", exist_ok=True)
-    os.chdir("/tmp/dgvcc_bench")
+    logs = tempfile.mkdtemp(prefix="dgvcc_bench_")  # the trainer's log dir: a directory of this run's own
+    os.chdir(logs)
     trainer = DGTrainer(2112 + rank, f"bench_r{rank}", dev, 1000, 10000, mode)
     os.chdir(cwd)
     batch = synthetic(B, H, W, dev, seed=1000 + rank)
@@ -330,6 +376,8 @@ def run_leg(args, precision, dev, world, rank):
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
     K.set_conv_timer(None)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, model, last)
     res = {"elapsed": elapsed, "last_loss": last, "mode": mode, "model": type(model).__name__}
     if world > 1:
         torch.cuda.synchronize()
@@ -356,7 +404,7 @@ def run_leg(args, precision, dev, world, rank):
     res.update(conv_ms=conv_ms, conv_flops=conv_flops, conv_n=conv_n, conv_bytes=conv_bytes,
                wg_ms=wg_ms, wg_flops=wg_flops, enc_ms=enc_ms, enc_flops=enc_flops,
                enc_gemm_ms=enc_gemm_ms, enc_gemm_flops=enc_gemm_flops)
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
         # data-parallel sanity check outside the timed region: identical parameters on every rank
         chk = torch.stack([p.detach().double().sum() for p in model.parameters()]).sum().reshape(1)
@@ -367,6 +415,7 @@ def run_leg(args, precision, dev, world, rank):
     views = 2 if (mode in ("final", "base") and not args.trunk) else 1
     res["frames"] = B * views * world * args.steps
     del model, opt, trainer, batch
+    shutil.rmtree(logs, ignore_errors=True)
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     return res
@@ -828,7 +877,7 @@ def main():
 
     prec = args.precision
     leg = "fp32_exact" if prec == "fp32" and args.f32_math == "exact" else prec
-    r = run_leg(args, leg, dev, world, rank)
+    r = run_leg(args, leg, dev, world, rank, dump_dir=args.dump_outputs)
     value = r["frames"] / r["elapsed"]
     workload = (f"{r['model']} {r['mode']}-mode DGTrainer.train_step (configs/baselines/sta_{args.trunk}.yml)"
                 if args.trunk else
@@ -868,7 +917,8 @@ def main():
         out["params_in_sync"] = r["params_in_sync"]
     if "allreduce" in r:  # the gradient all-reduce: bucketed and overlapped with the backward
         out["config"]["allreduce"] = r["allreduce"]
-    if leg == "fp32" and not args.no_f32_exact:
+    # everything below takes runs of its own: only with --full
+    if args.full and leg == "fp32" and not args.no_f32_exact:
         re_ = run_leg(args, "fp32_exact", dev, world, rank)
         out["f32_exact"] = {"value": round(re_["frames"] / re_["elapsed"], 3), "unit": "frames/s", "dtype": "fp32",
                             "ms_per_step": round(re_["elapsed"] / args.steps * 1e3, 3),
@@ -876,7 +926,7 @@ def main():
                             "last_loss": re_["last_loss"], "roofline": roofline(args, "fp32_exact", re_)}
         K_ = __import__("dgvcc_amd.kernels", fromlist=["call"])
         K_.call("dg_set_f32_math", F32_MATH_MODE[args.f32_math])
-    if prec == "fp32" and not args.no_bf16:
+    if args.full and prec == "fp32" and not args.no_bf16:
         rb = run_leg(args, "bf16", dev, world, rank)
         out["perf_bf16"] = {"value": round(rb["frames"] / rb["elapsed"], 3), "unit": "frames/s", "dtype": "bf16",
                             "ms_per_step": round(rb["elapsed"] / args.steps * 1e3, 3),
@@ -885,10 +935,10 @@ def main():
                             "last_loss": rb["last_loss"], "roofline": roofline(args, "bf16", rb)}
         if "params_in_sync" in rb:
             out["perf_bf16"]["params_in_sync"] = rb["params_in_sync"]
-    if rank == 0 and not args.trunk:
+    if args.full and rank == 0 and not args.trunk:
         out["dmap"] = dmap_roofline(args, dev)
         out["bl"] = bl_timing(args, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.trunk:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.trunk:
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         __import__("dgvcc_amd.kernels", fromlist=["call"]).call("dg_set_f32_math", F32_MATH_MODE[args.f32_math])
     if rank == 0:

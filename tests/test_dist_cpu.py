@@ -205,3 +205,37 @@ def test_bench_launcher_dry_run_world8():
     assert len(att["step_ms_per_rank"]) == 8 and len(att["exposed_ms_per_rank"]) == 8
     assert 0 < att["step_ms_min"] <= att["step_ms_max"] and att["exposed_ms"] >= 0
     assert att["step_ms_max"] == max(att["step_ms_per_rank"])
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.dump_outputs on a CPU module: loss as float64, parameters then float buffers as float32
+    state, gradients (zeros where a parameter has none), tensors above the per-tensor cap sampled
+    at the same seeded indices in both files and in every call."""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    try:
+        import bench
+    finally:
+        sys.path.remove(root)
+    torch.manual_seed(5)
+    m = torch.nn.Sequential(torch.nn.Linear(40, 30), torch.nn.BatchNorm1d(30), torch.nn.Linear(30, 2))
+    for p in list(m.parameters())[:-1]:
+        p.grad = torch.randn_like(p)
+    bench.dump_outputs(str(tmp_path / "a"), m, 1.25, cap=700)  # 6 parameters + 2 float buffers -> 87 elements per tensor at most
+    bench.dump_outputs(str(tmp_path / "b"), m, 1.25, cap=700)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "state", "grads")}
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")), n
+    assert a["loss"].dtype == np.float64 and a["loss"].tolist() == [1.25]
+    assert a["state"].dtype == np.float32 and a["grads"].dtype == np.float32
+    sizes = [min(p.numel(), 87) for p in m.parameters()]
+    bufs = [min(b.numel(), 87) for b in m.buffers() if b.is_floating_point()]
+    assert a["grads"].size == sum(sizes) and a["state"].size == sum(sizes) + sum(bufs)
+    w, b0 = m[0].weight.detach(), m[0].bias.detach()
+    assert set(a["state"][:87].tolist()) <= set(w.reshape(-1).tolist())  # a sample of the first weight
+    assert np.array_equal(a["state"][87:117], b0.numpy()) and np.array_equal(a["grads"][87:117], m[0].bias.grad.numpy())
+    pos = [int((w.reshape(-1) == v).nonzero()[0]) for v in a["state"][:87].tolist()]
+    assert np.array_equal(a["grads"][:87], m[0].weight.grad.reshape(-1)[pos].numpy())  # same indices in both files
+    assert not a["grads"][-2:].any()  # the last bias has no gradient

@@ -44,7 +44,8 @@ def test_dp_syncbn_strong_scaling(dev):
 def test_bench_gpus_flag_launches_ranks(dev):
     env = dict(os.environ, DGVCC_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup",
-                        "1", "--batch", "2", "--height", "256", "--width", "256", "--no-cpu-baseline", "--no-bf16"],
+                        "1", "--batch", "2", "--height", "256", "--width", "256", "--full", "--no-cpu-baseline",
+                        "--no-bf16"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
