@@ -876,6 +876,51 @@ def iw_cov_var(fraw: torch.Tensor, hw: int, var: torch.Tensor, accumulate=False)
     call("dg_iw_cov_var", ptr(fraw), B, C, 1.0 / (hw - 1), ptr(var), int(accumulate), stream())
 
 
+def _f32_flat(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise DGError(f"{what}: a contiguous float32 device tensor is required")
+    return t
+
+
+def kmeans1d(sorted: torch.Tensor, k: int):
+    """Optimal 1-D k-means of the ascending f32 values `sorted` into k contiguous clusters
+    (dg_kmeans1d): (bounds int32 [k+1], centroids f32 [k], cost f64 [1]), all on device; cluster c
+    is sorted[bounds[c]:bounds[c+1]].  Stream-ordered, no host synchronisation."""
+    _f32_flat(sorted, "kmeans1d")
+    n, k = sorted.numel(), int(k)
+    dev = sorted.device
+    ws = query("dg_kmeans1d_workspace", n, k)
+    work = torch.empty(ws // 8 + 1, dtype=torch.float64, device=dev)
+    bounds = torch.empty(k + 1, dtype=torch.int32, device=dev)
+    centroids = torch.empty(k, dtype=torch.float32, device=dev)
+    cost = torch.empty(1, dtype=torch.float64, device=dev)
+    call("dg_kmeans1d", ptr(sorted), n, k, ptr(bounds), ptr(centroids), ptr(cost), ptr(work), stream())
+    return bounds, centroids, cost
+
+
+def iw_cluster_mask(v: torch.Tensor, sorted: torch.Tensor, bounds: torch.Tensor,
+                    prev_mask: torch.Tensor | None = None):
+    """The ISW sensitive-covariance mask of the values v (any shape) from the clustering `bounds`
+    of their ascending copy `sorted` (dg_iw_cluster_mask): (mask f32 shaped as v = v > the largest
+    value of cluster 0 [& prev_mask], num_sensitive f32 scalar = sum mask), on device."""
+    _f32_flat(v, "iw_cluster_mask")
+    _f32_flat(sorted, "iw_cluster_mask")
+    n = v.numel()
+    if sorted.numel() != n or bounds.dtype != torch.int32 or bounds.numel() < 2 or not bounds.is_cuda:
+        raise DGError("iw_cluster_mask: sorted must hold v's values and bounds be a device int32 [k+1]")
+    if prev_mask is not None:
+        _f32_flat(prev_mask, "iw_cluster_mask")
+        if prev_mask.numel() != n:
+            raise DGError("iw_cluster_mask: prev_mask must have v's size")
+    ws = query("dg_kmeans1d_workspace", n, 1)
+    work = torch.empty(ws // 8 + 1, dtype=torch.float64, device=v.device)
+    mask = torch.empty_like(v)
+    ns = torch.empty((), dtype=torch.float32, device=v.device)
+    call("dg_iw_cluster_mask", ptr(v), ptr(sorted), ptr(bounds), n, ptr(prev_mask), ptr(mask), ptr(ns),
+         ptr(work), stream())
+    return mask, ns
+
+
 def sw_fwd(x: Act, mean_w, var_w, gamma, beta, running_mean, running_cov, training: bool,
            act: int, y: Act, T: int = 5, eps: float = 1e-5, momentum: float = 0.9) -> torch.Tensor:
     """SwitchWhiten2d (sw_type 2) forward; returns the `save` statistics buffer."""

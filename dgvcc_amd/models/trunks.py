@@ -348,7 +348,8 @@ class Bottleneck_ISW(nn.Module):
 
 
 class CovMatrix_ISW:
-    """models/ISW/cov_settings.py:16-89, device-resident (margin path, relax_denom > 0)."""
+    """models/ISW/cov_settings.py:16-89, device-resident: the margin path (relax_denom > 0) and
+    the kmeans1d clustering (relax_denom = 0; `centroids` keeps the last clustering's, on device)."""
 
     def __init__(self, dim, relax_denom=0, clusters=50):
         self.dim = dim
@@ -360,6 +361,7 @@ class CovMatrix_ISW:
         self.count_var_cov = 0
         self.mask_matrix = None
         self.num_sensitive = None
+        self.centroids = None
 
     def reset_mask_matrix(self):
         self.mask_matrix = None
@@ -368,8 +370,8 @@ class CovMatrix_ISW:
         if self.var_matrix is None:
             raise RuntimeError("no covariance statistics: run the model with cal_covstat=True first")
         if self.margin == 0:
-            raise NotImplementedError("relax_denom=0 (kmeans1d clustering) is parity-unpinned: "
-                                      "kmeans1d is not available offline")
+            self._set_mask_clustered()
+            return
         var = (self.var_matrix / self.count_var_cov).flatten()
         k = int(self.num_off_diagonal - self.margin)
         idx = torch.topk(var, k).indices  # device top-k over <= 512^2 entries, once per epoch
@@ -380,6 +382,19 @@ class CovMatrix_ISW:
             m = (self.mask_matrix.int() & m.int()).float()
         self.mask_matrix = m
         self.num_sensitive = m.sum()
+        self.var_matrix = None
+        self.count_var_cov = 0
+
+    def _set_mask_clustered(self):
+        """relax_denom = 0 (cov_settings.py:57-61): the mean variances clustered by optimal 1-D
+        k-means (dg_kmeans1d) and everything above cluster 0 marked sensitive (dg_iw_cluster_mask;
+        values tied with cluster 0's largest stay in cluster 0).  All on the caller's stream: the
+        sort is torch's, k-means, mask and count are ours, nothing is copied to the host."""
+        from .. import kernels as K
+        var = self.var_matrix / self.count_var_cov
+        srt = torch.sort(var.flatten()).values
+        bounds, self.centroids, _ = K.kmeans1d(srt, self.clusters)
+        self.mask_matrix, self.num_sensitive = K.iw_cluster_mask(var, srt, bounds, self.mask_matrix)
         self.var_matrix = None
         self.count_var_cov = 0
 

@@ -448,6 +448,29 @@ int dg_iw_loss(const float* fraw, int B, int C, float inv_hw1, float eps, const 
 /* cal_covstat: var[C][C] (+)= unbiased variance over B of f_ij*[j>i]. */
 int dg_iw_cov_var(const float* fraw, int B, int C, float inv_hw1, float* var, int accumulate,
                   void* stream);
+/* CovMatrix_ISW.set_mask_matrix with relax_denom = 0 (models/ISW/cov_settings.py:57-61, the
+ * `kmeans1d.cluster(var_flatten, clusters)` setting): optimal 1-D k-means of n ascending f32 values
+ * into k contiguous non-empty clusters, the partition of least within-cluster sum of squares, by an
+ * exact float64 dynamic programme (leftmost boundary on ties).  bounds [k + 1] ints: cluster c holds
+ * sorted[bounds[c] .. bounds[c + 1] - 1], bounds[0] = 0, bounds[k] = n; centroids [k] floats (may be
+ * NULL); cost: one double, the total sum of squares (may be NULL).  1 <= k <= 64, k <= n <= 2^20
+ * (DG_ERR_UNSUPPORTED beyond, DG_ERR_INVALID for k < 1 or n < k; nothing launched).  Workspace:
+ * dg_kmeans1d_workspace(n, k) bytes.  Every launch ends whatever the values hold (NaN included; the
+ * partition is then meaningless). */
+int64_t dg_kmeans1d_workspace(int n, int k);
+int dg_kmeans1d(const float* sorted, int n, int k, int* bounds, float* centroids, double* cost,
+                void* workspace, void* stream);
+/* The sensitive-covariance mask from that clustering: mask[e] = v[e] > sorted[bounds[1] - 1] (the
+ * largest value of cluster 0) over the n values v in their own order, ANDed with prev_mask (may be
+ * NULL; may alias mask) as set_mask_matrix does from the second epoch on, and *num_sensitive = sum
+ * mask (fixed-order reduction).  Values equal to cluster 0's largest all fall into cluster 0, so a run
+ * of equal values straddling the first boundary (the structural zeros of the diagonal and the lower
+ * triangle) is masked out whole; away from such ties this is the reference's
+ * topk(var_flatten, n - clusters.count(0)).  Workspace: dg_kmeans1d_workspace(n, 1) bytes at least
+ * (the clustering's own workspace serves; its contents are overwritten). */
+int dg_iw_cluster_mask(const float* v, const float* sorted, const int* bounds, int n,
+                       const float* prev_mask, float* mask, float* num_sensitive,
+                       void* workspace, void* stream);
 /* SwitchWhiten2d sw_type 2 (BW+IW), 16 channels per group, C <= 256
  * (models/SW/ops/switchwhiten.py:84-183).  mean_w/var_w: raw sw_mean_weight /
  * sw_var_weight (softmax inside).  running_mean [G][16], running_cov [G][16][16] updated
