@@ -642,24 +642,14 @@ __global__ __launch_bounds__(NT, 2) void conv_gen_kernel(GenArgs a) {
   }
 }
 
-static bool gen_parity() {  // DGVCC_GEN_PARITY=0: strided dgrad as one transposed gather (A/B switch)
-  const char* e = getenv("DGVCC_GEN_PARITY");
-  return !(e && e[0] == '0');
-}
-
 static bool f32_split();
-// DGVCC_GEN_SPLIT=0: f32 strided / general convs on v_mfma_f32_16x16x4_f32 also under the split
-// math (read per launch: A/B)
-static bool gen_split() {
-  const char* e = getenv("DGVCC_GEN_SPLIT");
-  return !(e && e[0] == '0');
-}
 
+// f32 under the split math: SPL = 1; a strided dgrad: one launch per output parity class
 template <typename T>
 int launch_gen(const GenArgs& a0, hipStream_t st) {
   bool spl = false;
-  if constexpr (!Is16<T>::value) spl = f32_split() && gen_split();
-  const int ncls = (a0.mode == 1 && a0.stride > 1 && gen_parity()) ? a0.stride * a0.stride : 1;
+  if constexpr (!Is16<T>::value) spl = f32_split();
+  const int ncls = (a0.mode == 1 && a0.stride > 1) ? a0.stride * a0.stride : 1;
   for (int c = 0; c < ncls; ++c) {
     GenArgs a = a0;
     long long M = (long long)a.N * a.P * a.Q;
@@ -726,7 +716,9 @@ constexpr int PSTAGES = 3;
 // EPI selects the epilogue at compile time (each variant's registers stay out of the
 // others'; runtime branches on all four spilled the 256-wide kernel): 0 = bias / accumulate /
 // statistics, 1 = split-K f32 partials, 2 = BN-backward partials (dgrad), 3 = eval BN+ReLU.
-template <int BN, int STG, int VAR = 0, int EPI = 0, typename T = bf16>
+// The DMA of the K-step PF ahead is issued after the first k-half's MFMAs, the MFMA blocks under
+// s_setprio(1).
+template <int BN, int STG, int EPI = 0, typename T = bf16>
 __global__ __launch_bounds__(512, 1) void conv_fwd_pipe_kernel(FwdArgs a) {
   constexpr int BK = 64;                    // bf16 channels per K-step (128-B rows)
   constexpr int AI = BN / 64;               // A (weight) DMA instructions per wave per K-step
@@ -821,7 +813,6 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pipe_kernel(FwdArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (VAR != 2 && t + PF < KT) PIPE_ISSUE(t + PF, (t + PF) % STG);
     const char* As = smem + (t % STG) * STAGE;
     const char* Bs = As + BN * 128;
 #pragma unroll
@@ -832,15 +823,13 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pipe_kernel(FwdArgs a) {
       for (int j = 0; j < TJ; ++j) bfr[j] = *(const u4v*)(Bs + swz(wpx + 16 * j + fr, ch));
 #pragma unroll
       for (int i = 0; i < TI; ++i) af[i] = *(const u4v*)(As + swz(wco + 16 * i + fr, ch));
-      if constexpr (VAR >= 1) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
         for (int j = 0; j < TJ; ++j) mfma_frag<T>(acc[i][j], af[i], bfr[j]);
-      if constexpr (VAR >= 1) __builtin_amdgcn_s_setprio(0);
-      if constexpr (VAR == 2) {
-        if (ks == 0 && t + PF < KT) PIPE_ISSUE(t + PF, (t + PF) % STG);
-      }
+      __builtin_amdgcn_s_setprio(0);
+      if (ks == 0 && t + PF < KT) PIPE_ISSUE(t + PF, (t + PF) % STG);
     }
   }
 #undef PIPE_ISSUE
@@ -930,7 +919,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pipe_kernel(FwdArgs a) {
   if constexpr (EPI == 2) epi_bnbwd<TI, TJ, 4, BN, T>(acc, valid, wid & 3, wco, wpx, smem, a, px0, co0, tid, fr, fc);
 }
 
-// Persistent form of conv_fwd_pipe_kernel (VAR 2 schedule): one block per CU walks its
+// Persistent form of conv_fwd_pipe_kernel (the same schedule): one block per CU walks its
 // tiles (block b, tiles b, b + G, ... through the same XCD remap) and keeps the LDS-DMA
 // ring running across tile boundaries: the next tile's first K-steps are issued during
 // the current tile's last ones, so its prologue latency hides under the current tile's
@@ -941,7 +930,7 @@ constexpr int PERS_BIAS_MAX = 1024;  // Cout limit of the persistent forward (LD
 // split (dg_common.h split3_8): one 32-channel K-step is one 16x16x32 block, the lane's 8
 // k values being its chunks fc and 4 + fc of the 128-B row for both operands.
 // Tap validity of the B (pixel) DMA pieces of a persistent conv tile, for the incremental
-// addressing (INC): the image-bounds test of tap (r, s) is separable, so each piece keeps 6 bits,
+// addressing: the image-bounds test of tap (r, s) is separable, so each piece keeps 6 bits,
 // rows r = 0..2 at bits 0..2 and columns s = 0..2 at bits 3..5, five pieces per 32-bit word
 // (R, S <= 3).  Tap (r, s) of piece i is inside the image iff both of need(r, s) << 6 (i % 5) are set.
 template <int BI>
@@ -963,12 +952,11 @@ __device__ __forceinline__ bool tapmask_ok(const TapMask<BI>& t, int i, unsigned
   return (t.w[i / 5] & nd) == nd;
 }
 
-// INC: incremental DMA addressing as in conv_fwd_psplit_kernel (DGVCC_PERS_INC=0 restores the per-K-step
-// recomputation)
+// The DMA addressing is incremental, as in conv_fwd_psplit_kernel.
 // WIDE (16-bit, BN = 128): 384-pixel tiles with the 8 waves all on pixels, each 128 channels x 48
 // pixels (the 256-channel kernel's per-wave filter reuse; 1.5x the MFMAs per barrier of the 2 x 4
 // layout of 64 x 64 wave tiles), two stages of (16 + 48) KB (DGVCC_PERS_WIDE=0: the 2 x 4 layout).
-template <int BN, int STG, int EPI = 0, typename T = bf16, int SPL = 0, int INC = 1, int WIDE = 0, int WST = 0>
+template <int BN, int STG, int EPI = 0, typename T = bf16, int SPL = 0, int WIDE = 0, int WST = 0>
 __global__ __launch_bounds__(512, 1) void conv_fwd_pers_kernel(FwdArgs a) {
   static_assert(!WIDE || (BN == 128 && SPL == 0 && STG == 2), "WIDE: the 16-bit 128-channel kernel");
   constexpr int PB = WIDE ? 384 : PBM;   // pixels per tile
@@ -1016,9 +1004,9 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pers_kernel(FwdArgs a) {
   struct Ctx {
     int px0, co0;
     __amdgpu_buffer_rsrc_t xr, wr;
-    int pp[BI], pq[BI], prow[BI];
-    unsigned bofs;        // INC: piece 0's window byte offset (piece i: + 8 i rows)
-    TapMask<BI> tm;       // INC: the pieces' in-image taps
+    int pp[BI], pq[BI], prow[BI];  // the pieces' image row / column and window row (read by setup only)
+    unsigned bofs;        // piece 0's window byte offset (piece i: + 8 i rows)
+    TapMask<BI> tm;       // the pieces' in-image taps
   };
   auto setup = [&](int lin, Ctx& c) {
     const int t = xcd_remap(lin, ntile);
@@ -1038,14 +1026,11 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pers_kernel(FwdArgs a) {
       c.prow[i] = m - plo;
       c.pp[i] = (m < M) ? rem / a.W : -100000;
       c.pq[i] = rem % a.W;
-      if constexpr (INC) {
-        if (i == 0) c.bofs = (unsigned)((long long)c.prow[0] * a.ldx * ES) + cbytes;
-        tapmask_set<BI>(c.tm, i, c.pp[i], c.pq[i], a);
-      }
+      if (i == 0) c.bofs = (unsigned)((long long)c.prow[0] * a.ldx * ES) + cbytes;
+      tapmask_set<BI>(c.tm, i, c.pp[i], c.pq[i], a);
     }
   };
-  const int RS = a.R * a.S;
-  // INC: the K-step of the next DMA issue as three digits, fastest first: (s, r, cb) in the
+  // the K-step of the next DMA issue as three digits, fastest first: (s, r, cb) in the
   // channel-block-major order (a.korder), (cb, s, r) in the tap-major one
   const bool ko = a.korder != 0;
   const int L0 = ko ? a.S : CB, L1 = ko ? a.R : a.S;
@@ -1077,30 +1062,10 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pers_kernel(FwdArgs a) {
   // the step PF ahead of consumed step t, possibly the next tile's
   auto issue_ahead = [&](const Ctx& c, const Ctx& n, int t, bool hn, unsigned stage) {
     const int u = t + PF;
-    if constexpr (INC) {
-      if (u < KT) issue_inc(c, stage);
-      else if (hn) {
-        if (u == KT) d0 = d1 = d2 = 0;
-        issue_inc(n, stage);
-      }
-    }
-  };
-  auto issue = [&](const Ctx& c, int kt, int stage) {
-    const int rs = a.korder ? kt % RS : kt / CB, cb = a.korder ? kt / RS : kt - rs * CB;
-    const int r = rs / a.S, s2 = rs - r * a.S;
-    char* As = smem + stage * STAGE;
-    char* Bs = As + BN * 128;
-    const unsigned kofs = (unsigned)((rs * a.C + cb * BK) * ES);
-#pragma unroll
-    for (int i = 0; i < AI; ++i) lds_dma16(c.wr, As + (wid * AI + i) * 1024, aoff[i] + kofs);
-    const int dh = r - a.pad, dw = s2 - a.pad;
-#pragma unroll
-    for (int i = 0; i < BI; ++i) {
-      const int hh = c.pp[i] + dh, ww = c.pq[i] + dw;
-      const bool ok = (unsigned)hh < (unsigned)a.H && (unsigned)ww < (unsigned)a.W;
-      const unsigned off =
-          ok ? (unsigned)(((long long)(c.prow[i] + dh * a.W + dw) * a.ldx + cb * BK) * ES) + cbytes : 0xFFFFFFF0u;
-      lds_dma16(c.xr, Bs + (wid * BI + i) * 1024, off);
+    if (u < KT) issue_inc(c, stage);
+    else if (hn) {
+      if (u == KT) d0 = d1 = d2 = 0;
+      issue_inc(n, stage);
     }
   };
 
@@ -1122,13 +1087,8 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pers_kernel(FwdArgs a) {
   const int wpx = (wid % NPXG) * (PB / NPXG), wco = (wid / NPXG) * (BN / NCOG);
   const int fr = lane & 15, fc = lane >> 4;
   unsigned gs = 0;  // K-steps issued/consumed across all tiles of this block
-  if constexpr (INC) {
-    issue_inc(cur, 0);
-    if (PF > 1) issue_inc(cur, 1);
-  } else {
-    issue(cur, 0, 0);
-    if (PF > 1) issue(cur, 1, 1);
-  }
+  issue_inc(cur, 0);
+  if (PF > 1) issue_inc(cur, 1);
   bool first_tile = true;
   while (true) {
     f4v acc[TI][TJ];
@@ -1160,12 +1120,8 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pers_kernel(FwdArgs a) {
         }
         // A fragments one row block ahead of their MFMAs (all TI at once spill at BN = 256)
         u4v a0 = *(const u4v*)(As + swz(wco + fr, fc)), a1 = *(const u4v*)(As + swz(wco + fr, 4 + fc));
-        if constexpr (INC) issue_ahead(cur, nxt, t, has_next, (gs + PF) % STG);
-        else {  // the step PF ahead (its stage was last read before this step's barrier)
-          const int u = t + PF;
-          if (u < KT) issue(cur, u, (gs + PF) % STG);
-          else if (has_next) issue(nxt, u - KT, (gs + PF) % STG);
-        }
+        // the step PF ahead (its stage was last read before this step's barrier)
+        issue_ahead(cur, nxt, t, has_next, (gs + PF) % STG);
         s8v bh[TJ][3];
 #pragma unroll
         for (int j = 0; j < TJ; ++j) split3_8(b0[j], b1[j], bh[j][0], bh[j][1], bh[j][2]);
@@ -1202,14 +1158,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pers_kernel(FwdArgs a) {
 #pragma unroll
           for (int j = 0; j < TJ; ++j) mfma_frag<T>(acc[i][j], af[i], bfr[j]);
         __builtin_amdgcn_s_setprio(0);
-        if (ks == 0) {  // the step PF ahead, possibly the next tile's
-          if constexpr (INC) issue_ahead(cur, nxt, t, has_next, (gs + PF) % STG);
-          else {
-            const int u = t + PF;
-            if (u < KT) issue(cur, u, (gs + PF) % STG);
-            else if (has_next) issue(nxt, u - KT, (gs + PF) % STG);
-          }
-        }
+        if (ks == 0) issue_ahead(cur, nxt, t, has_next, (gs + PF) % STG);  // possibly the next tile's
       }
     }
     first_tile = false;
@@ -1337,27 +1286,15 @@ constexpr int PSB = 192;  // pixels per tile of the pre-split kernel at BN = 256
 // BN = 128: 384-pixel tiles with the 8 waves all on pixels (each 128 channels x 48 pixels, the
 // BN = 256 kernel's wave tile), two stages of (24 + 48) KB: the filter fragments are reused by 8
 // waves instead of 4 (the 192-pixel 2 x 4 layout ran 52% MFMA-busy against 65% at BN = 256)
-__host__ __device__ constexpr int psplit_psb(int BN, int wide = 1) { return BN == 128 && wide ? 384 : PSB; }
-static bool psplit_wide() {  // DGVCC_PSPLIT_WIDE=0: BN = 128 on 192-pixel tiles of 2 x 4 waves
-  const char* e = getenv("DGVCC_PSPLIT_WIDE");
-  return !(e && e[0] == '0');
-}
-static bool pers_inc() {  // DGVCC_PERS_INC=0: the persistent 16-bit forward with per-K-step addressing (A/B)
-  const char* e = getenv("DGVCC_PERS_INC");
-  return !(e && e[0] == '0');
-}
+__host__ __device__ constexpr int psplit_psb(int BN) { return BN == 128 ? 384 : PSB; }
 // the incremental addressing's tap masks hold R, S <= 3
 static bool inc_shape_ok(const FwdArgs& a) { return a.R <= 3 && a.S <= 3; }
-static bool psplit_inc() {  // DGVCC_PSPLIT_INC=0: per-K-step recomputed DMA addressing (read per launch: A/B)
-  const char* e = getenv("DGVCC_PSPLIT_INC");
-  return !(e && e[0] == '0');
-}
-// INC = 1: the DMA of each K-step is addressed incrementally.  The issue cursor (r, s, cb) steps
+// The DMA of each K-step is addressed incrementally.  The issue cursor (r, s, cb) steps
 // through the K order without divisions, and each B piece keeps its tile-constant window byte
 // offset plus a bit mask of the taps that stay inside the image (bit r * S + s), so a K-step's
-// B offsets are one scalar tap/channel offset added per piece.  INC = 0 (DGVCC_PSPLIT_INC=0)
-// recomputes kt -> (rs, cb) and each piece's bounds check and offset at every K-step: ~130
-// scalar and ~30 vector instructions in front of the split on every wave.
+// B offsets are one scalar tap/channel offset added per piece (recomputing kt -> (rs, cb) and
+// each piece's bounds check and offset at every K-step cost ~130 scalar and ~30 vector
+// instructions in front of the split on every wave).
 // TALL = 1 (BN = 256, EPI 0): 256-pixel tiles, each wave 128 channels x 64 pixels (TJ = 4), so every
 // filter fragment read and every staged filter byte feeds 4 pixel blocks instead of 3.  The two
 // 80-KB stages fill the LDS; the epilogue's statistics scratch and this tile's bias live in the
@@ -1388,10 +1325,9 @@ static bool psplit_inc() {  // DGVCC_PSPLIT_INC=0: per-K-step recomputed DMA add
 // in its MFMA block and one in its prologue, where SCH 0 keeps both in the same phase (the stamp build
 // put their prologues at 28% / 66% of the K-step).  A tile ends with a drain phase (waves 4-7's last
 // MFMA block) before the shared epilogue.  The same fragments and MFMA order: bit-identical to SCH 0.
-template <int BN, int STG, int EPI = 0, int WIDE = 1, int INC = 1, int TALL = 0, int HM = 0, int STAMP = 0,
-          int SCH = 0>
+template <int BN, int STG, int EPI = 0, int TALL = 0, int HM = 0, int STAMP = 0, int SCH = 0>
 __global__ __launch_bounds__(512, 1) void conv_fwd_psplit_kernel(FwdArgs a, const char* __restrict__ wsp) {
-  static_assert(!TALL || (BN == 256 && EPI == 0 && STG == 2 && INC), "TALL: 256-channel training forward only");
+  static_assert(!TALL || (BN == 256 && EPI == 0 && STG == 2), "TALL: 256-channel training forward only");
   static_assert(SCH != 5 || (TALL && HM), "SCH 5: the TALL f16 x3 kernel");
   static_assert(SCH != 6 || (TALL && HM && STG == 2 && !STAMP), "SCH 6: the TALL f16 x3 kernel");
   static_assert(SCH != 7 || (TALL && HM), "SCH 7: diagnostic timing of the TALL f16 x3 kernel without the split");
@@ -1411,8 +1347,8 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_psplit_kernel(FwdArgs a, cons
   constexpr bool RSTG = SCH == 5;
   constexpr int NPL = HM ? 2 : 3;  // filter planes
   constexpr int KB = NPL * 64;     // bytes per (output channel, 32-deep k-block) of the planes
-  constexpr int PSB = TALL ? 256 : psplit_psb(BN, WIDE);
-  constexpr int NCOG = (BN == 128 && WIDE) ? 1 : 2;  // channel groups of waves
+  constexpr int PSB = TALL ? 256 : psplit_psb(BN);
+  constexpr int NCOG = BN == 128 ? 1 : 2;          // channel groups of waves
   constexpr int NPXG = 8 / NCOG;                   // pixel groups of waves
   constexpr int AROWB = 64;                        // bytes per A plane row (32 bf16)
   constexpr int A_BYTES = NPL * BN * AROWB;
@@ -1464,9 +1400,9 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_psplit_kernel(FwdArgs a, cons
   struct Ctx {
     int px0, co0;
     __amdgpu_buffer_rsrc_t xr, wr;
-    int pp[BI], pq[BI], prow0;  // INC = 0: piece i's window row: prow0 + 8 i
-    unsigned bofs;        // INC = 1: window byte offset of piece 0's row (piece i: + 8 i rows + its chunk)
-    TapMask<BI> tm;       // INC = 1: the pieces' in-image taps
+    int pp[BI], pq[BI], prow0;  // the pieces' image row / column, piece 0's window row (read by setup only)
+    unsigned bofs;        // window byte offset of piece 0's row (piece i: + 8 i rows + its chunk)
+    TapMask<BI> tm;       // the pieces' in-image taps
   };
   auto setup = [&](int lin, Ctx& c) {
     const int t = xcd_remap(lin, ntile);
@@ -1492,14 +1428,11 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_psplit_kernel(FwdArgs a, cons
       const int rem = m % HW;
       c.pp[i] = (m < M) ? rem / a.W : -100000;
       c.pq[i] = rem % a.W;
-      if constexpr (INC) {
-        if (i == 0) c.bofs = (unsigned)((long long)c.prow0 * a.ldx * 4);
-        tapmask_set<BI>(c.tm, i, c.pp[i], c.pq[i], a);
-      }
+      if (i == 0) c.bofs = (unsigned)((long long)c.prow0 * a.ldx * 4);
+      tapmask_set<BI>(c.tm, i, c.pp[i], c.pq[i], a);
     }
   };
-  const int RS = a.R * a.S;
-  // INC = 1: K-step of the next DMA issue as three digits, fastest first, advanced without
+  // K-step of the next DMA issue as three digits, fastest first, advanced without
   // divisions: (s, r, cb) in the channel-block-major order (a.korder), (cb, s, r) in the tap-major one
   const bool ko = a.korder != 0;
   const int L0 = ko ? a.S : CB, L1 = ko ? a.R : a.S;
@@ -1576,24 +1509,6 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_psplit_kernel(FwdArgs a, cons
                                                           : 0xFFFFFFF0u);
     }
   };
-  auto issue = [&](const Ctx& c, int kt, int stage) {
-    const int rs = a.korder ? kt % RS : kt / CB, cb = a.korder ? kt / RS : kt - rs * CB;
-    const int r = rs / a.S, s2 = rs - r * a.S;
-    char* As = smem + stage * STAGE;
-    char* Bs = As + A_BYTES;
-#pragma unroll
-    for (int q = 0; q < AI; ++q)
-      lds_dma16s(c.wr, As + (wid * AI + q) * 1024, alane + (unsigned)((rs * CB + cb) * KB), aoff_s(q));
-    const int dh = r - a.pad, dw = s2 - a.pad;
-#pragma unroll
-    for (int i = 0; i < BI; ++i) {
-      const int hh = c.pp[i] + dh, ww = c.pq[i] + dw;
-      const bool ok = (unsigned)hh < (unsigned)a.H && (unsigned)ww < (unsigned)a.W;
-      const unsigned off =
-          ok ? (unsigned)(((long long)((c.prow0 + 8 * i) + dh * a.W + dw) * a.ldx + cb * 32) * 4) + cbytes[i] : 0xFFFFFFF0u;
-      lds_dma16(c.xr, Bs + (wid * BI + i) * 1024, off);
-    }
-  };
 
   int lin = blockIdx.x;
   if (lin >= ntile) return;
@@ -1620,12 +1535,9 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_psplit_kernel(FwdArgs a, cons
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     store_stage(0);
     load_inc(cur);
-  } else if constexpr (INC) {
+  } else {
     issue_inc(cur, 0);
     if (PF > 1) issue_inc(cur, 1);
-  } else {
-    issue(cur, 0, 0);
-    if (PF > 1) issue(cur, 1, 1);
   }
   bool first_tile = true;
   unsigned long long st_sum[5] = {0, 0, 0, 0, 0}, st_prev = 0, st_nk = 0, st_tiles = 0;
@@ -1826,15 +1738,10 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_psplit_kernel(FwdArgs a, cons
         if (dma_nxt && u_dma == KT) d0 = d1 = d2 = 0;
       } else {
         const int u = u_dma;
-        if constexpr (INC) {
-          if (u < KT) issue_inc(cur, (gs + PF) % STG);
-          else if (has_next) {
-            if (u == KT) d0 = d1 = d2 = 0;
-            issue_inc(nxt, (gs + PF) % STG);
-          }
-        } else {
-          if (u < KT) issue(cur, u, (gs + PF) % STG);
-          else if (has_next) issue(nxt, u - KT, (gs + PF) % STG);
+        if (u < KT) issue_inc(cur, (gs + PF) % STG);
+        else if (has_next) {
+          if (u == KT) d0 = d1 = d2 = 0;
+          issue_inc(nxt, (gs + PF) % STG);
         }
       }
       s8v bh[TJ][NPL];
@@ -2872,6 +2779,9 @@ __global__ __launch_bounds__(1024) void splitk_reduce_kernel(const float* __rest
   }
 }
 
+// output channels per tile of the pipelined / persistent forwards (Cout % 64 == 0)
+static int conv_bn(int Cout) { return Cout % 256 == 0 ? 256 : (Cout % 128 == 0 ? 128 : 64); }
+
 // K-slices for a pipelined bf16 forward whose tile grid cannot fill the chip (deep
 // layers at small batch: 3k-25k pixels): the split minimising a cost model of the K loop
 // against the reduce traffic, keeping one wave of blocks (<= 256, one 128-KB-LDS block per
@@ -2880,7 +2790,7 @@ static int fwd_ksplit(long long M, int Cout, int C, int R, int S) {
   const char* e = getenv("DGVCC_SPLITK");
   if (e && e[0] == '0') return 1;
   if (C % 64 != 0) return 1;
-  const int BN = Cout % 256 == 0 ? 256 : (Cout % 128 == 0 ? 128 : 64);
+  const int BN = conv_bn(Cout);
   if (Cout == 64 || BN == 64) return 1;
   const long long nblk = (M + 255) / 256 * (Cout / BN);
   if (nblk >= 128) return 1;
@@ -2910,19 +2820,11 @@ static bool use_persist() {
   return v == 1;
 }
 
-// DGVCC_SHORTK_REG=1: 16-bit forwards with <= 2 K-steps (the ResNet trunks' 1x1 convs from 64
-// or 128 channels, HBM-bound) on the register-staged two-blocks-per-CU kernel (A/B switch)
-static bool short_k_reg() {
-  const char* e = getenv("DGVCC_SHORTK_REG");
-  return e && e[0] == '1';
-}
-
 // DGVCC_F32_PERSIST=0: f32 forwards on the register-staged conv_fwd_kernel (A/B switch)
 static bool use_f32_persist() {
   const char* e = getenv("DGVCC_F32_PERSIST");
   return !(e && e[0] == '0');
 }
-static int f32_pers_bn(int Cout);
 static bool f32_pers_ok(const FwdArgs& a);
 static bool f32_pers_shape_ok(const FwdArgs& a, int kmin);
 
@@ -2951,41 +2853,9 @@ static int persist_grid() {  // one block per CU (the ring takes most of the LDS
   return g;
 }
 
-static int pipe_var() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DGVCC_PIPE_VAR");
-    v = e ? atoi(e) : 2;
-  }
-  return v;
-}
-
-static bool pipe_wide() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DGVCC_CONV_WIDE");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
 static bool use_tap3() {
   const char* e = getenv("DGVCC_TAP3");
   return !(e && e[0] == '0');
-}
-
-static bool use_wgrad_pipe() {
-  const char* e = getenv("DGVCC_WGRAD_PIPE");
-  return e && e[0] == '1';
-}
-
-static bool use_pipe() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DGVCC_CONV_PIPE");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
 }
 
 // ---------------------------------------------------------------------------
@@ -3476,16 +3346,8 @@ static bool use_tap3p() {
 
 // K-step width of the 3-tap kernels: 64 channels on row-aligned tiles (768x1024: the 32-ch
 // kernel's forwards were 0.27 ms/step faster but the step 0.07 ms slower, same-box A/B), 32 on
-// the padded index (320-px final-mode training: +1%, conv 9.74 -> 9.51 ms/step).
-// DGVCC_TAP3_BK=32|64 forces one.
-static int tap3_bk(bool padk) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DGVCC_TAP3_BK");
-    v = e ? atoi(e) : 0;
-  }
-  return v == 32 || v == 64 ? v : (padk ? 32 : 64);
-}
+// the padded index (320-px final-mode training: +1%, conv 9.74 -> 9.51 ms/step): the launcher
+// takes conv_fwd_tap3_kernel<0> and conv_fwd_tap3n_kernel<1>.
 
 // the padded 3-tap variant: whole-tensor x descriptor (32-bit byte offsets), no split-K
 static bool tap3_pad_ok(const FwdArgs& a) {
@@ -3495,8 +3357,6 @@ static bool tap3_pad_ok(const FwdArgs& a) {
   const long long M = (long long)a.N * a.H * a.W;
   return M * a.ldx * 2 < (1ll << 31) && (long long)a.N * (a.H + 2) * (a.W + 2) < (1ll << 30);
 }
-
-static int f32_pers_bn(int Cout) { return Cout % 256 == 0 && pipe_wide() ? 256 : (Cout % 128 == 0 ? 128 : 64); }
 
 // DGVCC_PSPLIT=0: split-math f32 forwards split the filter per wave (conv_fwd_pers_kernel SPL=1)
 static bool use_psplit() {
@@ -3520,13 +3380,13 @@ static bool psplit_shortk() {
   return !(e && e[0] == '0');
 }
 static bool psplit_ok(const FwdArgs& a) {
-  if (!(use_psplit() && f32_split() && f32_pers_shape_ok(a, psplit_shortk() ? 2 : 3) && f32_pers_bn(a.Cout) >= 128 &&
+  if (!(use_psplit() && f32_split() && f32_pers_shape_ok(a, psplit_shortk() ? 2 : 3) && conv_bn(a.Cout) >= 128 &&
         (long long)a.Cout * a.R * a.S * a.C * 6 < (1ll << 31)))
     return false;
   const int mt = psplit_min_tiles();
   if (mt <= 0) return f32_pers_ok(a);
   const long long M = (long long)a.N * a.H * a.W;
-  return (long long)dg_cdiv(M, psplit_tile_px(a)) * (a.Cout / f32_pers_bn(a.Cout)) >= mt;
+  return (long long)dg_cdiv(M, psplit_tile_px(a)) * (a.Cout / conv_bn(a.Cout)) >= mt;
 }
 
 // The f16 x3 pre-split forward reads its pixel operand pre-split by split_x_h_kernel (SCH 8) when
@@ -3555,19 +3415,19 @@ static int psplit_tall_mode() {
 // rounds of 256-pixel tiles costing no more than the 192-pixel ones at ~5% less time per pixel
 static bool psplit_tall(const FwdArgs& a) {
   const int mode = psplit_tall_mode();
-  if (mode == 0 || f32_pers_bn(a.Cout) != 256 || a.escale || a.bpart || !psplit_inc()) return false;
+  if (mode == 0 || conv_bn(a.Cout) != 256 || a.escale || a.bpart) return false;
   if (mode == 2) return true;
   const long long M = (long long)a.N * a.H * a.W, nco = a.Cout / 256, G = persist_grid();
   const long long r256 = dg_cdiv(dg_cdiv(M, 256) * nco, G), r192 = dg_cdiv(dg_cdiv(M, PSB) * nco, G);
   return (double)r256 * 256 * 0.95 < (double)r192 * PSB;
 }
 // pixels per tile of the pre-split launch (and so rows of its epilogue statistics)
-static int psplit_tile_px(const FwdArgs& a) { return psplit_tall(a) ? 256 : psplit_psb(f32_pers_bn(a.Cout), psplit_wide()); }
+static int psplit_tile_px(const FwdArgs& a) { return psplit_tall(a) ? 256 : psplit_psb(conv_bn(a.Cout)); }
 
 // f32 split-math shapes served by conv_fwd_rsplit_kernel (64-wide channel tiles)
 static bool rsplit_ok(const FwdArgs& a) {
   return use_psplit() && f32_split() && a.ksplit <= 1 && !a.bpart && a.C % 32 == 0 && a.ldx % 4 == 0 &&
-         a.Cout % 64 == 0 && f32_pers_bn(a.Cout) == 64 && (long long)a.Cout * a.R * a.S * a.C * 6 < (1ll << 31);
+         a.Cout % 64 == 0 && conv_bn(a.Cout) == 64 && (long long)a.Cout * a.R * a.S * a.C * 6 < (1ll << 31);
 }
 
 // rows of W % 256 == 0 of a 3x3 / pad-1 Cout = 64 conv: the 3-tap strip kernel (DGVCC_RSPLIT3=0 off;
@@ -3658,7 +3518,7 @@ static bool f32_pers_shape_ok(const FwdArgs& a, int kmin) {
 static bool f32_pers_ok(const FwdArgs& a) {
   if (!f32_pers_shape_ok(a, 3)) return false;
   const long long M = (long long)a.N * a.H * a.W;
-  return (long long)dg_cdiv(M, PBM) * (a.Cout / f32_pers_bn(a.Cout)) > 256;
+  return (long long)dg_cdiv(M, PBM) * (a.Cout / conv_bn(a.Cout)) > 256;
 }
 
 static int conv_korder() {  // DGVCC_CONV_KORDER=0/1 (read per launch: same-process A/B)
@@ -3690,14 +3550,14 @@ static bool pers_wide_small() {
   return !(e && e[0] == '0');
 }
 static bool pers16_wide(const FwdArgs& a) {
-  if (!(pers_wide_on() && use_pipe() && a.C % 64 == 0 && a.ldx % 8 == 0 &&
-        !(short_k_reg() && a.R * a.S * (a.C / 64) <= 2) && (long long)a.Cout * a.R * a.S * a.C * 2 < (1ll << 31) &&
-        a.ksplit <= 1 && !a.bpart && use_persist() && pipe_var() == 2 && inc_shape_ok(a) &&
+  if (!(pers_wide_on() && a.C % 64 == 0 && a.ldx % 8 == 0 &&
+        (long long)a.Cout * a.R * a.S * a.C * 2 < (1ll << 31) &&
+        a.ksplit <= 1 && !a.bpart && use_persist() && inc_shape_ok(a) &&
         a.R * a.S * (a.C / 64) >= pers16_kmin(2) && a.Cout <= PERS_BIAS_MAX))
     return false;
   if (a.Cout % 128 != 0) return false;
   const long long M = (long long)a.N * a.H * a.W;
-  if (!(a.Cout % 256 == 0 && pipe_wide())) return (long long)dg_cdiv(M, PBM) * (a.Cout / 128) > 2 * 256;  // BN = 128
+  if (a.Cout % 256 != 0) return (long long)dg_cdiv(M, PBM) * (a.Cout / 128) > 2 * 256;  // BN = 128
   // 256-channel launches too small for the 256-channel persistent forward (<= 2 rounds of 256 x 256
   // tiles, which then ran one tile per block on the pipe kernel: 384 tiles = 1.5 rounds at 1/16
   // resolution): the 384 x 128 tiles where they cost fewer tile-areas of rounds (+10% for the
@@ -3738,23 +3598,20 @@ template <typename T>
 int launch_fwd_impl(const FwdArgs& a, hipStream_t st) {
   const long long M = (long long)a.N * a.H * a.W;
   if constexpr (Is16<T>::value) {
-    if (use_pipe() && a.C % 64 == 0 && a.ldx % 8 == 0 && !(short_k_reg() && a.R * a.S * (a.C / 64) <= 2) &&
-        (long long)a.Cout * a.R * a.S * a.C * 2 < (1ll << 31)) {
+    if (a.C % 64 == 0 && a.ldx % 8 == 0 && (long long)a.Cout * a.R * a.S * a.C * 2 < (1ll << 31)) {
       const int np = dg_cdiv(M, PBM);
-      const int var = pipe_var();
+      const int bn = conv_bn(a.Cout);
       const int epi = a.ksplit > 1 ? 1 : a.bpart ? 2 : a.escale ? 3 : 0;
 #define PIPE_LAUNCH(BN_, STG_, G_) \
       do { \
-        if (epi == 1) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 2, 1, T>), dim3(G_), dim3(512), 0, st, a); \
-        else if (epi == 2) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 2, 2, T>), dim3(G_), dim3(512), 0, st, a); \
-        else if (epi == 3) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 2, 3, T>), dim3(G_), dim3(512), 0, st, a); \
-        else if (var == 1) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 1, 0, T>), dim3(G_), dim3(512), 0, st, a); \
-        else if (var == 2) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 2, 0, T>), dim3(G_), dim3(512), 0, st, a); \
-        else hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 0, 0, T>), dim3(G_), dim3(512), 0, st, a); \
+        if (epi == 1) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 1, T>), dim3(G_), dim3(512), 0, st, a); \
+        else if (epi == 2) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 2, T>), dim3(G_), dim3(512), 0, st, a); \
+        else if (epi == 3) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 3, T>), dim3(G_), dim3(512), 0, st, a); \
+        else hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN_, STG_, 0, T>), dim3(G_), dim3(512), 0, st, a); \
       } while (0)
       if (a.ksplit > 1) {  // BN and stage count as the unsplit choice below
-        const unsigned g = (unsigned)(np * (a.Cout / (a.Cout % 256 == 0 && pipe_wide() ? 256 : 128)) * a.ksplit);
-        if (a.Cout % 256 == 0 && pipe_wide()) PIPE_LAUNCH(256, 2, g);
+        const unsigned g = (unsigned)(np * (a.Cout / (bn == 256 ? 256 : 128)) * a.ksplit);
+        if (bn == 256) PIPE_LAUNCH(256, 2, g);
         else PIPE_LAUNCH(128, 3, g);
         DG_CHECK_LAUNCH();
         hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)dg_cdiv(M, 256), a.Cout / 64), dim3(1024), 0, st,
@@ -3769,17 +3626,13 @@ int launch_fwd_impl(const FwdArgs& a, hipStream_t st) {
             hipLaunchKernelGGL((conv_fwd_tap3p_kernel<2, T>), dim3((unsigned)std::min<long long>(M / 512, g)), dim3(512), 0, st, a);
           else
             hipLaunchKernelGGL((conv_fwd_tap3p_kernel<1, T>), dim3(g), dim3(512), 0, st, a);
-        } else if (tap3_bk(false) == 32) hipLaunchKernelGGL((conv_fwd_tap3n_kernel<0, T>), dim3((unsigned)(M / 256)), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv_fwd_tap3_kernel<0, T>), dim3((unsigned)(M / 256)), dim3(256), 0, st, a);
+        } else hipLaunchKernelGGL((conv_fwd_tap3_kernel<0, T>), dim3((unsigned)(M / 256)), dim3(256), 0, st, a);
       } else if (a.Cout == 64 && a.R == 3 && a.S == 3 && a.pad == 1 && !a.part && tap3_pad_ok(a)) {
         const long long U = (long long)a.N * (a.H + 2) * (a.W + 2);
-        if (tap3_bk(true) == 32) hipLaunchKernelGGL((conv_fwd_tap3n_kernel<1, T>), dim3((unsigned)dg_cdiv(U, 256)), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv_fwd_tap3_kernel<1, T>), dim3((unsigned)dg_cdiv(U, 256)), dim3(256), 0, st, a);
-      } else if (use_persist() && !a.bpart && var == 2 && inc_shape_ok(a) &&
-                 a.R * a.S * (a.C / 64) >= pers16_kmin(a.Cout % 256 == 0 && pipe_wide() ? 2 : 3) && a.Cout <= PERS_BIAS_MAX &&
-                 (long long)np * (a.Cout / (a.Cout % 256 == 0 && pipe_wide() ? 256 : (a.Cout % 128 == 0 ? 128 : 64))) >
-                     2 * 256) {
-        const int bn = a.Cout % 256 == 0 && pipe_wide() ? 256 : (a.Cout % 128 == 0 ? 128 : 64);
+        hipLaunchKernelGGL((conv_fwd_tap3n_kernel<1, T>), dim3((unsigned)dg_cdiv(U, 256)), dim3(256), 0, st, a);
+      } else if (use_persist() && !a.bpart && inc_shape_ok(a) &&
+                 a.R * a.S * (a.C / 64) >= pers16_kmin(bn == 256 ? 2 : 3) && a.Cout <= PERS_BIAS_MAX &&
+                 (long long)np * (a.Cout / bn) > 2 * 256) {
         const long long tiles = (long long)np * (a.Cout / bn);
         const unsigned g = (unsigned)std::min<long long>(tiles, persist_grid());
         if (epi == 3) {
@@ -3788,28 +3641,22 @@ int launch_fwd_impl(const FwdArgs& a, hipStream_t st) {
           else hipLaunchKernelGGL((conv_fwd_pers_kernel<64, 3, 3, T>), dim3(g), dim3(512), 0, st, a);
         } else if (bn == 128 && pers16_wide(a)) {
           const unsigned gw = (unsigned)std::min<long long>((long long)dg_cdiv(M, 384) * (a.Cout / 128), persist_grid());
-          if (a.wide_st) hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 2, 0, T, 0, 1, 1, 1>), dim3(gw), dim3(512), 0, st, a);
-          else hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 2, 0, T, 0, 1, 1>), dim3(gw), dim3(512), 0, st, a);
-        } else {
-          if (!pers_inc()) {  // A/B: per-K-step recomputed DMA addressing
-            if (bn == 256) hipLaunchKernelGGL((conv_fwd_pers_kernel<256, 2, 0, T, 0, 0>), dim3(g), dim3(512), 0, st, a);
-            else if (bn == 128) hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 3, 0, T, 0, 0>), dim3(g), dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((conv_fwd_pers_kernel<64, 3, 0, T, 0, 0>), dim3(g), dim3(512), 0, st, a);
-          } else if (bn == 256 && a.wide_st) hipLaunchKernelGGL((conv_fwd_pers_kernel<256, 2, 0, T, 0, 1, 0, 1>), dim3(g), dim3(512), 0, st, a);
-          else if (bn == 256) hipLaunchKernelGGL((conv_fwd_pers_kernel<256, 2, 0, T>), dim3(g), dim3(512), 0, st, a);
-          else if (bn == 128 && a.wide_st && pers_wst() == 3)
-            hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 3, 0, T, 0, 1, 0, 1>), dim3(g), dim3(512), 0, st, a);
-          else if (bn == 128) hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 3, 0, T>), dim3(g), dim3(512), 0, st, a);
-          else if (a.wide_st && pers_wst() == 3)
-            hipLaunchKernelGGL((conv_fwd_pers_kernel<64, 3, 0, T, 0, 1, 0, 1>), dim3(g), dim3(512), 0, st, a);
-          else hipLaunchKernelGGL((conv_fwd_pers_kernel<64, 3, 0, T>), dim3(g), dim3(512), 0, st, a);
-        }
+          if (a.wide_st) hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 2, 0, T, 0, 1, 1>), dim3(gw), dim3(512), 0, st, a);
+          else hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 2, 0, T, 0, 1>), dim3(gw), dim3(512), 0, st, a);
+        } else if (bn == 256 && a.wide_st) hipLaunchKernelGGL((conv_fwd_pers_kernel<256, 2, 0, T, 0, 0, 1>), dim3(g), dim3(512), 0, st, a);
+        else if (bn == 256) hipLaunchKernelGGL((conv_fwd_pers_kernel<256, 2, 0, T>), dim3(g), dim3(512), 0, st, a);
+        else if (bn == 128 && a.wide_st && pers_wst() == 3)
+          hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 3, 0, T, 0, 0, 1>), dim3(g), dim3(512), 0, st, a);
+        else if (bn == 128) hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 3, 0, T>), dim3(g), dim3(512), 0, st, a);
+        else if (a.wide_st && pers_wst() == 3)
+          hipLaunchKernelGGL((conv_fwd_pers_kernel<64, 3, 0, T, 0, 0, 1>), dim3(g), dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((conv_fwd_pers_kernel<64, 3, 0, T>), dim3(g), dim3(512), 0, st, a);
       } else if (epi == 0 && pers16_wide(a)) {  // small 256-channel grids on 384 x 128 persistent tiles
         const unsigned gw = (unsigned)std::min<long long>((long long)dg_cdiv(M, 384) * (a.Cout / 128), persist_grid());
-        if (a.wide_st) hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 2, 0, T, 0, 1, 1, 1>), dim3(gw), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 2, 0, T, 0, 1, 1>), dim3(gw), dim3(512), 0, st, a);
-      } else if (a.Cout % 256 == 0 && pipe_wide()) PIPE_LAUNCH(256, 2, np * (a.Cout / 256));
-      else if (a.Cout % 128 == 0) PIPE_LAUNCH(128, 3, np * (a.Cout / 128));
+        if (a.wide_st) hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 2, 0, T, 0, 1, 1>), dim3(gw), dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((conv_fwd_pers_kernel<128, 2, 0, T, 0, 1>), dim3(gw), dim3(512), 0, st, a);
+      } else if (bn == 256) PIPE_LAUNCH(256, 2, np * (a.Cout / 256));
+      else if (bn == 128) PIPE_LAUNCH(128, 3, np * (a.Cout / 128));
       else PIPE_LAUNCH(64, 3, np * (a.Cout / 64));
 #undef PIPE_LAUNCH
       DG_CHECK_LAUNCH();
@@ -3820,16 +3667,16 @@ int launch_fwd_impl(const FwdArgs& a, hipStream_t st) {
     if (a.bpart) {  // dgrad with the BN-backward partials in the epilogue: the pre-split kernel only
       FwdArgs q = a;
       q.bpart = nullptr;
-      if (!(psplit_ok(q) && psplit_wide() && has_split_room(a))) return DG_ERR_UNSUPPORTED;
+      if (!(psplit_ok(q) && has_split_room(a))) return DG_ERR_UNSUPPORTED;
       const bool h16 = f32_h16();
       const unsigned short* wsp = h16 ? presplit_h(a, st) : presplit(a, st);
       if (!wsp) return DG_ERR_HIP;
-      const int bn2 = f32_pers_bn(a.Cout);
+      const int bn2 = conv_bn(a.Cout);
       const unsigned g2 = (unsigned)std::min<long long>((long long)dg_cdiv(M, psplit_psb(bn2)) * (a.Cout / bn2),
                                                         persist_grid());
       if (h16) {
-        if (bn2 == 256) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 2, 1, 1, 0, 1>), dim3(g2), dim3(512), 0, st, a, (const char*)wsp);
-        else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, 2, 1, 1, 0, 1>), dim3(g2), dim3(512), 0, st, a, (const char*)wsp);
+        if (bn2 == 256) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 2, 0, 1>), dim3(g2), dim3(512), 0, st, a, (const char*)wsp);
+        else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, 2, 0, 1>), dim3(g2), dim3(512), 0, st, a, (const char*)wsp);
       } else if (bn2 == 256) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 2>), dim3(g2), dim3(512), 0, st, a, (const char*)wsp);
       else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, 2>), dim3(g2), dim3(512), 0, st, a, (const char*)wsp);
       DG_CHECK_LAUNCH();
@@ -3870,7 +3717,7 @@ int launch_fwd_impl(const FwdArgs& a, hipStream_t st) {
     // hides the DMA latency comfortably.  Epilogue BN statistics (a.part) as in 16-bit.
     if (f32_pers_ok(a) || (psplit_ok(a) && has_split_room(a))) {
       const int np = dg_cdiv(M, PBM);
-      const int bn = f32_pers_bn(a.Cout);
+      const int bn = conv_bn(a.Cout);
       const long long tiles = (long long)np * (a.Cout / bn);
       const unsigned g = (unsigned)std::min<long long>(tiles, persist_grid());
 #define F32_PERS(SPL_) \
@@ -3887,17 +3734,14 @@ int launch_fwd_impl(const FwdArgs& a, hipStream_t st) {
       } while (0)
       if (f32_split() && psplit_ok(a) && has_split_room(a)) {
         const bool tall = psplit_tall(a);
-        const bool wide = psplit_wide();
-        const bool inc = psplit_inc();
-        // f16 x3 planes instead (presplit_h) on the default (incremental, wide) forms
-        const bool h16 = f32_h16() && inc && wide;
+        const bool h16 = f32_h16();  // f16 x3 planes instead (presplit_h)
         // the producer's pair image (the conv's scale from the producer's bound)
         const bool pair = h16 && a.xpair && a.xbound && !a.escale && !(g_stamps && getenv("DGVCC_PSPLIT_STAMP"));
         FwdArgs ah = a;
         if (pair) ah.xamax = a.xbound;
         const unsigned short* wsp = h16 ? presplit_h(ah, st) : presplit(a, st);
         if (!wsp) return DG_ERR_HIP;
-        const int bn2 = f32_pers_bn(a.Cout);
+        const int bn2 = conv_bn(a.Cout);
         const unsigned g2 = (unsigned)std::min<long long>((long long)dg_cdiv(M, psplit_tile_px(a)) * (a.Cout / bn2),
                                                           persist_grid());
         const char* wspc = (const char*)wsp;
@@ -3930,45 +3774,40 @@ int launch_fwd_impl(const FwdArgs& a, hipStream_t st) {
 #define PSPLIT_LAUNCH(EPI_)                                                                                    \
   do {                                                                                                         \
     if (h16 && xs) {                                                                                           \
-      if (bn2 == 256) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, EPI_, 1, 1, 0, 1, 0, 8>), dim3(g2), dim3(512), 0, st, ap, wspc); \
-      else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, EPI_, 1, 1, 0, 1, 0, 8>), dim3(g2), dim3(512), 0, st, ap, wspc); \
+      if (bn2 == 256) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, EPI_, 0, 1, 0, 8>), dim3(g2), dim3(512), 0, st, ap, wspc); \
+      else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, EPI_, 0, 1, 0, 8>), dim3(g2), dim3(512), 0, st, ap, wspc); \
     } else if (h16) {                                                                                          \
-      if (bn2 == 256) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, EPI_, 1, 1, 0, 1>), dim3(g2), dim3(512), 0, st, ap, wspc); \
-      else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, EPI_, 1, 1, 0, 1>), dim3(g2), dim3(512), 0, st, ap, wspc); \
-    } else if (bn2 == 256) {                                                                                   \
-      if (inc) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, EPI_>), dim3(g2), dim3(512), 0, st, ap, wspc); \
-      else hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, EPI_, 1, 0>), dim3(g2), dim3(512), 0, st, ap, wspc); \
-    } else if (wide) {                                                                                         \
-      if (inc) hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, EPI_>), dim3(g2), dim3(512), 0, st, ap, wspc); \
-      else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, EPI_, 1, 0>), dim3(g2), dim3(512), 0, st, ap, wspc); \
-    } else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 3, EPI_, 0>), dim3(g2), dim3(512), 0, st, ap, wspc);  \
+      if (bn2 == 256) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, EPI_, 0, 1>), dim3(g2), dim3(512), 0, st, ap, wspc); \
+      else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, EPI_, 0, 1>), dim3(g2), dim3(512), 0, st, ap, wspc); \
+    } else if (bn2 == 256) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, EPI_>), dim3(g2), dim3(512), 0, st, ap, wspc); \
+    else hipLaunchKernelGGL((conv_fwd_psplit_kernel<128, 2, EPI_>), dim3(g2), dim3(512), 0, st, ap, wspc);     \
   } while (0)
         if (a.escale) PSPLIT_LAUNCH(3);
         else if (h16 && tall && g_stamps && getenv("DGVCC_PSPLIT_STAMP") &&
                  (long long)g2 * 8 * 8 * 8 <= g_stamp_bytes) {  // diagnostic stamp build (tools/stamp_psplit.py)
           ap.stamps = g_stamps;
           const int sch = psplit_sch();
-          if (sch == 5 && a.R * a.S * (a.C / 32) >= 2) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 1, 5>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 4) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 1, 4>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 3) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 1, 3>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 2) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 1, 2>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 1) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 1, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          if (sch == 5 && a.R * a.S * (a.C / 32) >= 2) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 5>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 4) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 4>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 3) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 3>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 2) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 2>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 1) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
         } else if (h16 && tall && xs) {
-          hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 8>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 8>), dim3(g2), dim3(512), 0, st, ap, wspc);
         } else if (h16 && tall) {
           const int sch = psplit_sch();
-          if (sch == 9) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 9>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 6) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 6>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 7) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 7>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 5 && a.R * a.S * (a.C / 32) >= 2) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 5>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 4) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 4>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 3) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 3>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 2) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 2>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else if (sch == 1) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1, 0, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
-          else hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          if (sch == 9) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 9>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 6) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 6>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 7) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 7>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 5 && a.R * a.S * (a.C / 32) >= 2) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 5>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 4) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 4>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 3) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 3>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 2) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 2>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else if (sch == 1) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 0, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
+          else hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
         }
-        else if (tall) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1, 1, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
+        else if (tall) hipLaunchKernelGGL((conv_fwd_psplit_kernel<256, 2, 0, 1>), dim3(g2), dim3(512), 0, st, ap, wspc);
         else PSPLIT_LAUNCH(0);
 #undef PSPLIT_LAUNCH
       } else if (f32_split()) F32_PERS(1);
@@ -4457,19 +4296,21 @@ __global__ __launch_bounds__(NTH, 512 / NTH) void conv_wgrad_split_kernel(WgArgs
 // one image row (W % 32 == 0); dY[32 px][BCO] and the input strip X[34 px][BC] of image row
 // p + r - 1 (columns q0 - 1 .. q0 + 32) are split once into bf16 planes, and the taps s = 0, 1, 2
 // read the strip at row offsets s.  Per staged value 3x the MFMA work of the per-tap kernel.
-// 64 x 64 (x 3 taps): 4 waves of 32 x 32, two blocks per CU (the per-tap kernel's 64-wide tiles
-// were bound by the split and LDS-store work, ~30% MFMA-busy); 128 x 128: 8 waves of 64 x 32,
-// one block per CU.
-// NR = 3 (the 64-channel layers, 8 waves of 32 x 16 x 9 taps): a block owns all three kernel rows,
-// staging the dY rows once and the three X strips of image rows p - 1, p, p + 1 per K-step, instead
-// of three blocks (one per kernel row) each staging and splitting the same dY rows: 33% less split
-// and staging work per MFMA (DGVCC_WGRAD_SPLIT9=0: the 64 x 64 x 3-tap blocks).
+// One block of 512 threads per CU.  128 x 128, NR = 1: 8 waves of 64 x 32, one kernel row per block.
+// 64 x 64, NR = 3 (the 64-channel layers, 8 waves of 32 x 16 x 9 taps): a block owns all three
+// kernel rows, staging the dY rows once and the three X strips of image rows p - 1, p, p + 1 per
+// K-step, instead of three blocks (one per kernel row) each staging and splitting the same dY
+// rows: 33% less split and staging work per MFMA.
+// The next step's split + LDS stores run after the first tap's MFMA block (after tap 1, or dY
+// after tap 0 and X after tap 1, measured slower: wgrad 0.59 -> 0.60 of the ceiling,
+// profiles/round2g/wgrad3_swp_ab.txt).
 // HM = 1: the f16 x3 arithmetic (dg_common.h): dY and X scaled by their tensors' powers of two
 // (a.dyam / a.xam) and split into two f16 planes each, three MFMAs per block, the slab written
 // back at 2^-(e_dy + e_x).
-template <int BCO, int BC, int WCO, int NTH, int SWP = 0, int NR = 1, int HM = 0>
-__global__ __launch_bounds__(NTH, 512 / NTH) void conv_wgrad_split3_kernel(WgArgs a) {
+template <int BCO, int BC, int NR = 1, int HM = 0>
+__global__ __launch_bounds__(512, 1) void conv_wgrad_split3_kernel(WgArgs a) {
   static_assert(NR == 1 || NR == 3, "one kernel row per block, or all three");
+  constexpr int WCO = 2, NTH = 512;  // output-channel wave groups; threads
   constexpr int BKP = 32, XR = BKP + 2;
   constexpr int ROWA = BCO * 2 + 32, ROWB = BC * 2 + 32;  // bytes per bf16 plane row
   constexpr int PA = BKP * ROWA, PB = XR * ROWB;           // bytes per plane
@@ -4559,11 +4400,11 @@ __global__ __launch_bounds__(NTH, 512 / NTH) void conv_wgrad_split3_kernel(WgArg
       if (++sp == a.H) { sp = 0; ++sn; }
     }
   };
-  auto swrite = [&](int buf, int part = 3) __attribute__((always_inline)) {
+  auto swrite = [&](int buf) __attribute__((always_inline)) {
     char* As = smem + buf * TILE;
     char* Bs = As + NPL * PA;
 #pragma unroll
-    for (int i = 0; i < AR * (part & 1); ++i) {
+    for (int i = 0; i < AR; ++i) {
       const int idx = tid + NTH * i;
       const int o = (idx / CPRA) * ROWA + (idx % CPRA) * 8;
       if constexpr (HM) {
@@ -4580,7 +4421,7 @@ __global__ __launch_bounds__(NTH, 512 / NTH) void conv_wgrad_split3_kernel(WgArg
       }
     }
 #pragma unroll
-    for (int i = 0; i < BR * ((part >> 1) & 1); ++i) {
+    for (int i = 0; i < BR; ++i) {
       const int idx = tid + NTH * i;
       if (idx < NR * XR * CPRB) {
         const int strip = NR == 3 ? idx / (XR * CPRB) : 0, sidx = idx - strip * (XR * CPRB);
@@ -4670,15 +4511,9 @@ __global__ __launch_bounds__(NTH, 512 / NTH) void conv_wgrad_split3_kernel(WgArg
             for (int j = 0; j < TJ; ++j)
               acc[rs][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i][PA6[u]], bh[j][PB6[u]], acc[rs][i][j], 0, 0, 0);
       }
-      // one block per CU: the next step's split + LDS stores between the taps' MFMA blocks
-      if (NTH == 512 && kt + 1 < nkt) {
-        if (SWP == 0 && rs == 1) swrite(cur ^ 1);
-        if (SWP == 1 && rs == 0) swrite(cur ^ 1, 1);
-        if (SWP == 1 && rs == 1) swrite(cur ^ 1, 2);
-        if (SWP == 2 && rs == 0) swrite(cur ^ 1);
-      }
+      // one block per CU: the next step's split + LDS stores after the first tap's MFMA block
+      if (kt + 1 < nkt && rs == 0) swrite(cur ^ 1);
     }
-    if (NTH != 512 && kt + 1 < nkt) swrite(cur ^ 1);  // two blocks per CU overlap each other instead
     __syncthreads();
   }
 
@@ -4756,13 +4591,9 @@ static int wgs3_tile(int C, int Cout, int R, int S, int W) {
 }
 static bool wgs3_shape_ok(int C, int Cout, int R, int S, int W) { return wgs3_tile(C, Cout, R, S, W) != 0; }
 static long long wgs3_tiles(int C, int Cout, int b) { return (long long)(Cout / b) * (C / b) * 3; }
-// the 64-tile layers on the 9-tap (all three kernel rows per block) form: DGVCC_WGRAD_SPLIT9=0 off
-static bool wgs9_on(int b3) {
-  if (b3 != 64) return false;
-  const char* e = getenv("DGVCC_WGRAD_SPLIT9");
-  return !(e && e[0] == '0');
-}
+// the 64-tile layers run the 9-tap form (all three kernel rows per block, one block per CU)
 static long long wgs9_tiles(int C, int Cout) { return (long long)(Cout / 64) * (C / 64); }
+// (b = 64: the plan of two 3-tap 64-tile blocks per CU, which only the workspace query still covers)
 static long long wgs3_slots(int b) { return b == 64 ? 512 : 256; }
 
 __global__ void wgrad_reduce_kernel(const float* __restrict__ slab, int splits, int Cout, int C, int RS,
@@ -4791,176 +4622,11 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ slab, int splits, 
   }
 }
 
-// bf16 weight gradient, pipelined: 8 waves (2 co x 4 c) over a BCO x BC tile of
-// one (r,s) tap, K = 64 pixels per step.  dY and X pixel rows are staged by
-// LDS-DMA into a 3-stage ring (one raw barrier per step, counted vmcnt) and read
-// transposed with ds_read_b64_tr_b16.  Rows are unpadded (DMA images are
-// lane-linear); bank conflicts of the transposed reads are removed by an XOR
-// swizzle of the 16-B chunk index with the row (applied on the DMA source side).
+// LDS rows staged by LDS-DMA are unpadded (DMA images are lane-linear); bank conflicts of the
+// transposed reads (ds_read_b64_tr_b16) are removed by an XOR swizzle of the 16-B chunk index
+// with the row (CPR chunks per row), applied on the DMA source side.
 template <int CPR>
 __device__ __forceinline__ int wg_swz(int r) { return CPR >= 16 ? 2 * (r & 7) : 2 * ((r >> 1) & 3); }
-
-template <int BCO, int BC, typename T = bf16>
-__global__ __launch_bounds__(512, 1) void conv_wgrad_pipe_kernel(WgArgs a) {
-  constexpr int BKP = 64;
-  constexpr int RA = BCO * 2, RB = BC * 2;                 // bytes per LDS row
-  constexpr int CPRA = RA / 16, CPRB = RB / 16;            // 16-B chunks per row
-  constexpr int RPIA = 1024 / RA, RPIB = 1024 / RB;        // rows per DMA instruction
-  constexpr int AIw = BKP * RA / 1024 / 8, BIw = BKP * RB / 1024 / 8;   // DMA instr. per wave per step
-  constexpr int STAGE = BKP * (RA + RB);
-  constexpr int TI = BCO / 32, TJ = BC / 64;
-  static_assert(AIw >= 1 && BIw >= 1, "tile too small for 8 loader waves");
-  __shared__ __attribute__((aligned(1024))) char smem[PSTAGES * STAGE];
-
-  const int HW = a.H * a.W;
-  const int PQ = a.P * a.Q;
-  const int M = a.N * PQ;
-  const int RS = a.R * a.S;
-  const int nco = a.Cout / BCO, ncb = a.C / BC;
-  const int tiles = nco * ncb * RS;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = bid / tiles;
-  int t = bid - split * tiles;
-  const int cot = t % nco; t /= nco;
-  const int cbt = t % ncb;
-  const int rs = t / ncb;
-  const int co0 = cot * BCO, c0 = cbt * BC;
-  const int r = rs / a.S, s = rs - r * a.S;
-  const int dh = r - a.pad, dw = s - a.pad;
-  const int kbeg = split * a.pps;
-  const int kend = min(M, kbeg + a.pps);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-  const unsigned dy_bytes = (unsigned)(((long long)(kend - kbeg - 1) * a.lddy + a.Cout) * 2);
-  __amdgpu_buffer_rsrc_t dyr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.dy + (long long)kbeg * a.lddy * 2), 0, dy_bytes, 0x00020000);
-  const int halo = a.pad * (a.W + 1);
-  const int xlo = a.whole_x ? 0 : max(0, kbeg - halo);
-  const int xhi = a.whole_x ? a.N * HW : min(M, kend + halo);
-  const unsigned x_bytes = (unsigned)(((long long)(xhi - xlo - 1) * a.ldx + a.C) * 2);
-  __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.x + (long long)xlo * a.ldx * 2), 0, x_bytes, 0x00020000);
-
-  // DMA geometry of this lane: row within the instruction and the source chunk
-  const int arow = lane / CPRA, achunk = (lane % CPRA) ^ wg_swz<CPRA>(arow);
-  const int brow = lane / CPRB, bchunk = (lane % CPRB) ^ wg_swz<CPRB>(brow);
-  // (rows of instruction ii start at ii*RPI: RPI is a multiple of 8 or divides 8,
-  //  so wg_swz(ii*RPI + row) == wg_swz(row) whenever RPI >= 8 ... handled below)
-  const int nkt = (kend - kbeg + BKP - 1) / BKP;
-  int bn[BIw], bp[BIw], bq[BIw];  // output-grid coordinates of this lane's X rows at the next issue
-#pragma unroll
-  for (int i = 0; i < BIw; ++i) {
-    const int px = kbeg + (wid * BIw + i) * RPIB + brow;
-    bn[i] = px / PQ;
-    const int rem = px - bn[i] * PQ;
-    bp[i] = rem / a.Q;
-    bq[i] = rem - bp[i] * a.Q;
-  }
-
-#define WG_ISSUE(kt_, stage_) \
-  do { \
-    const int k0 = kbeg + (kt_) * BKP; \
-    char* As = smem + (stage_) * STAGE; \
-    char* Bs = As + BKP * RA; \
-    _Pragma("unroll") for (int i = 0; i < AIw; ++i) { \
-      const int ii = wid * AIw + i; \
-      const int row = ii * RPIA + arow; \
-      const int ch = (lane % CPRA) ^ wg_swz<CPRA>(row); \
-      const int px = k0 + row; \
-      const unsigned off = px < kend ? (unsigned)(((long long)(px - kbeg) * a.lddy + co0 + ch * 8) * 2) : 0xFFFFFFF0u; \
-      lds_dma16(dyr, As + ii * 1024, off); \
-    } \
-    _Pragma("unroll") for (int i = 0; i < BIw; ++i) { \
-      const int ii = wid * BIw + i; \
-      const int row = ii * RPIB + brow; \
-      const int ch = (lane % CPRB) ^ wg_swz<CPRB>(row); \
-      const int px = k0 + row; \
-      const int h = bp[i] * a.stride + dh, ww = bq[i] * a.stride + dw; \
-      const bool ok = px < kend && (unsigned)h < (unsigned)a.H && (unsigned)ww < (unsigned)a.W; \
-      const long long pin = (long long)bn[i] * HW + (long long)h * a.W + ww - xlo; \
-      const unsigned off = ok ? (unsigned)((pin * a.ldx + c0 + ch * 8) * 2) : 0xFFFFFFF0u; \
-      lds_dma16(xr, Bs + ii * 1024, off); \
-      /* advance this row's (n, p, q) by one K-step (64 pixels): no divisions in the loop */ \
-      bq[i] += BKP; \
-      while (bq[i] >= a.Q) { bq[i] -= a.Q; if (++bp[i] >= a.P) { bp[i] = 0; ++bn[i]; } } \
-    } \
-  } while (0)
-  (void)achunk; (void)bchunk;
-
-  f4v acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) acc[i][j] = f4v{0.f, 0.f, 0.f, 0.f};
-  const int wco = (wid >> 2) * (BCO / 2), wc = (wid & 3) * (BC / 4);
-  const int g = lane >> 4, q = (lane & 15) >> 2, p4 = lane & 3;
-
-  WG_ISSUE(0, 0);
-  if (nkt > 1) WG_ISSUE(1, 1);
-  for (int kt = 0; kt < nkt; ++kt) {
-    if (kt + 1 < nkt) {
-      if constexpr (AIw + BIw == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else if constexpr (AIw + BIw == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else if constexpr (AIw + BIw == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else if constexpr (AIw + BIw == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (kt + 2 < nkt) WG_ISSUE(kt + 2, (kt + 2) % PSTAGES);
-    const char* As = smem + (kt % PSTAGES) * STAGE;
-    const char* Bs = As + BKP * RA;
-#pragma unroll
-    for (int ks = 0; ks < BKP / 32; ++ks) {
-      const int r1 = 32 * ks + 4 * g + q, r2 = r1 + 16;
-      s8v af[TI], bfv[TJ];
-#pragma unroll
-      for (int i = 0; i < TI; ++i) {
-        const int cc = (wco + 16 * i) / 8 + (p4 >> 1);
-        const int hb = (p4 & 1) * 8;
-        s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (DG_LDS s4v*)(As + r1 * RA + ((cc ^ wg_swz<CPRA>(r1)) << 4) + hb));
-        s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (DG_LDS s4v*)(As + r2 * RA + ((cc ^ wg_swz<CPRA>(r2)) << 4) + hb));
-        af[i] = s8v{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) {
-        const int cc = (wc + 16 * j) / 8 + (p4 >> 1);
-        const int hb = (p4 & 1) * 8;
-        s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (DG_LDS s4v*)(Bs + r1 * RB + ((cc ^ wg_swz<CPRB>(r1)) << 4) + hb));
-        s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (DG_LDS s4v*)(Bs + r2 * RB + ((cc ^ wg_swz<CPRB>(r2)) << 4) + hb));
-        bfv[j] = s8v{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-          acc[i][j] = mfma16x16x32<T>(af[i], bfv[j], acc[i][j]);
-    }
-  }
-#undef WG_ISSUE
-
-  const long long ldk = (long long)RS * a.C;
-  float* out = a.slab + (long long)split * a.Cout * ldk;
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) {
-      const int c = c0 + wc + 16 * j + (lane & 15);
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int co = co0 + wco + 16 * i + 4 * g + rr;
-        out[co * ldk + rs * a.C + c] = acc[i][j][rr];
-      }
-    }
-}
 
 // ---------------------------------------------------------------------------
 // bf16 weight gradient of a 3x3 / stride 1 / pad 1 conv with all 9 taps fused in
@@ -4973,28 +4639,29 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pipe_kernel(WgArgs a) {
 // ---------------------------------------------------------------------------
 constexpr int W9_XROWS = 72;
 
-// WT = 1 (BCO 128): wave tile 64 co x 16 c (TI 4, TJ 1) instead of 32 x 32: the 9 taps' B
-// fragments are read once per 4 A fragments (fewer transposed LDS reads per MFMA).
-// WT = 2 (BCO 64): wave tile 64 co x 16 c, the 8 waves split as 4 channel groups x 2 k-halves
+// Wave tile 64 co x 16 c (TI 4, TJ 1): the 9 taps' B fragments are read once per 4 A fragments
+// (fewer transposed LDS reads per MFMA than 32 x 32 / 32 x 16 wave tiles, which read 22
+// transposed fragments per 18 MFMAs and left the 64-channel layer LDS-bound).
+// BCO 128: the 8 waves as 2 co x 4 c groups.  BCO 64 (KH): 4 channel groups x 2 k-halves
 // (wave group kh takes the 32-px k-substep kh of every K-step) and each k-half writes its own
-// f32 slab split (the reduce sums 2x the splits).  The 32 co x 16 c tile of WT = 0 read 22
-// transposed fragments per 18 MFMAs and left the 64-channel layer LDS-bound.
+// f32 slab split (the reduce sums 2x the splits).
 // PADK = 1 (W % 64 != 0, the 40/20-wide deep layers of 320-px crops): the K index runs over
 // the zero-padded image, u = (n, p+1, q+1) in N x (H+2) x (W+2), so a K-step of 64 u may
 // span rows and every shifted strip read lands on a zero pad cell exactly where the conv's
 // padding is: dy rows of pad cells are zero, x rows outside the image are zero.  Costs
 // (H+2)(W+2)/HW more K (10% at 40x40) instead of falling back to the per-tap kernel.
-// SCH (DMA issue point of the K-step after next): 0 = right after the barrier; 2 (default) =
-// after the first 32-px k-substep's MFMAs, MFMA blocks under s_setprio(1), as
-// conv_fwd_pipe_kernel (A/B in one call: wgrad 881 -> 949 TF/s, 15.1 -> 14.0 ms per step).
+// The DMA of the K-step after next is issued after the first 32-px k-substep's MFMAs, MFMA
+// blocks under s_setprio(1), as conv_fwd_pipe_kernel (against the issue right after the barrier:
+// wgrad 881 -> 949 TF/s, 15.1 -> 14.0 ms per step).
 // Measured and dropped: setprio alone (no change), priority without the moved issue (-0.7%),
 // the issue split over two points of the substep loop (777 TF/s).
-// INC (W % 64 == 0 path): the DMA addressing of a K-step is incremental: the step's row
+// W % 64 == 0 path: the DMA addressing of a K-step is incremental: the step's row
 // coordinates (n, p, q0) advance by 64 pixels without divisions, and each of the wave's <= 6
 // pieces keeps its lane-constant byte offset (and X row), so a piece costs one scalar-offset add
-// and, for X, a column test.  INC = 0 (DGVCC_WG9_INC=0) recomputes every piece each K-step.
-template <int BCO, int WT = 0, int PADK = 0, int SCH = 0, typename T = bf16, int INC = 1>
+// and, for X, a column test.
+template <int BCO, int PADK = 0, typename T = bf16>
 __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
+  static_assert(BCO == 128 || BCO == 64, "output-channel tile");
   constexpr int BKP = 64, BC = 64;
   constexpr int RA = BCO * 2, RX = BC * 2;                    // bytes per LDS row
   constexpr int CPRA = RA / 16, CPRX = RX / 16;
@@ -5004,9 +4671,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
   constexpr int N_INST = A_INST + X_INST;
   constexpr int A_BYTES = BKP * RA, X_BYTES = W9_XROWS * RX;
   constexpr int STAGE = A_BYTES + 3 * X_BYTES;
-  constexpr bool WIDE = BCO == 128 && WT == 1;
-  constexpr bool KH = BCO == 64 && WT == 2;
-  constexpr int TI = (WIDE || KH) ? 4 : 2, TJ = (BCO == 128 && !WIDE) ? 2 : 1;  // wave tile: 16*TI co x 16*TJ c, 9 taps
+  constexpr bool KH = BCO == 64;
+  constexpr int TI = 4, TJ = 1;  // wave tile: 16*TI co x 16*TJ c, 9 taps
   __shared__ __attribute__((aligned(1024))) char smem[PSTAGES * STAGE];
 
   const int HW = a.H * a.W;
@@ -5067,13 +4733,13 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
     } \
   } while (0)
 
-  // INC: the wave's pieces k (instruction ii = wid + 8 k): lane-constant source offsets, X rows
+  // !PADK: the wave's pieces k (instruction ii = wid + 8 k): lane-constant source offsets, X rows
   constexpr int KMAX = (N_INST + 7) / 8;
   constexpr int KA = A_INST / 8;  // pieces 0 .. KA-1 of every wave are dY rows (A_INST % 8 == 0)
   static_assert(A_INST % 8 == 0, "dY pieces must be whole rounds of the 8 waves");
   unsigned loff[KMAX];
   int xrow[KMAX], xdh[KMAX];
-  if constexpr (INC && !PADK) {
+  if constexpr (!PADK) {
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
       const int ii = wid + 8 * k;
@@ -5094,7 +4760,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
       }
     }
   }
-  // INC: image coordinates of the next issued K-step's first pixel (kbeg + issued * 64)
+  // !PADK: image coordinates of the next issued K-step's first pixel (kbeg + issued * 64)
   int in_ = kbeg / HW, ipr = (kbeg - in_ * HW) / a.W, iq0 = kbeg - in_ * HW - ipr * a.W, ipx = kbeg;
   // a.band: the K-steps walk bands of a.band image rows column block by column block, so two of a
   // step's three X strips are the previous step's (L2-hot) instead of a whole row of steps back;
@@ -5143,29 +4809,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
 
 #define W9_ISSUE(kt_, stage_) \
   do { \
-    if constexpr (PADK) { W9_ISSUE_PAD(kt_, stage_); break; } \
-    if constexpr (INC) { W9_ISSUE_INC(stage_); break; } \
-    const int px0 = kbeg + (kt_) * BKP; \
-    const int n = px0 / HW, rem = px0 - n * HW; \
-    const int pr = rem / a.W, q0 = rem - pr * a.W; \
-    char* As = smem + (stage_) * STAGE; \
-    char* Xs = As + A_BYTES; \
-    for (int ii = wid; ii < N_INST; ii += 8) { \
-      if (ii < A_INST) { \
-        const int row = ii * RPIA + lane / CPRA; \
-        const int ch = (lane % CPRA) ^ wg_swz<CPRA>(row); \
-        lds_dma16(dyr, As + ii * 1024, (unsigned)(((long long)(px0 + row - kbeg) * a.lddy + co0 + ch * 8) * 2)); \
-      } else { \
-        const int jj = ii - A_INST; \
-        const int dhi = jj / 9, sub = jj - dhi * 9; \
-        const int row = sub * 8 + (lane >> 3); \
-        const int ch = (lane & 7) ^ wg_swz<CPRX>(row); \
-        const int h = pr + dhi - 1, w = q0 - 4 + row; \
-        const bool ok = (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W; \
-        const long long pin = (long long)n * HW + (long long)h * a.W + w - xlo; \
-        lds_dma16(xr, Xs + dhi * X_BYTES + sub * 1024, ok ? (unsigned)((pin * a.ldx + c0 + ch * 8) * 2) : 0xFFFFFFF0u); \
-      } \
-    } \
+    if constexpr (PADK) W9_ISSUE_PAD(kt_, stage_); \
+    else W9_ISSUE_INC(stage_); \
   } while (0)
 
   f4v acc[9][TI][TJ];
@@ -5175,8 +4820,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
     for (int i = 0; i < TI; ++i)
 #pragma unroll
       for (int j = 0; j < TJ; ++j) acc[tp][i][j] = f4v{0.f, 0.f, 0.f, 0.f};
-  const int wco = KH ? 0 : WIDE ? (wid & 1) * 64 : (BCO == 128 ? (wid & 3) * 32 : (wid & 1) * 32);
-  const int wc = KH ? (wid & 3) * 16 : WIDE ? (wid >> 1) * 16 : (BCO == 128 ? (wid >> 2) * 32 : (wid >> 1) * 16);
+  const int wco = KH ? 0 : (wid & 1) * 64;
+  const int wc = KH ? (wid & 3) * 16 : (wid >> 1) * 16;
   const int kh = KH ? (wid >> 2) : 0;
   const int g = lane >> 4, qq = (lane & 15) >> 2, p4 = lane & 3;
   const int hb = (p4 & 1) * 8;
@@ -5195,13 +4840,12 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (SCH == 0 && kt + 2 < nkt) W9_ISSUE(kt + 2, (kt + 2) % PSTAGES);
     const char* As = smem + (kt % PSTAGES) * STAGE;
     const char* Xs = As + A_BYTES;
 #pragma unroll
     for (int ks = 0; ks < BKP / 32; ++ks) {
       if (!KH || ks == kh) {
-      if constexpr (SCH == 2) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
       const int r1 = 32 * ks + 4 * g + qq, r2 = r1 + 16;
       s8v af[TI];
 #pragma unroll
@@ -5237,11 +4881,9 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
                   mfma16x16x32<T>(af[i], bfv[j], acc[dhi * 3 + sw][i][j]);
         }
       }
-      if constexpr (SCH == 2) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       }
-      if constexpr (SCH == 2) {
-        if (ks == 0 && kt + 2 < nkt) W9_ISSUE(kt + 2, (kt + 2) % PSTAGES);
-      }
+      if (ks == 0 && kt + 2 < nkt) W9_ISSUE(kt + 2, (kt + 2) % PSTAGES);
     }
   }
 #undef W9_ISSUE
@@ -5265,40 +4907,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad9_kernel(WgArgs a) {
       }
 }
 
-static bool wg9_inc() {  // DGVCC_WG9_INC=0: per-K-step recomputed DMA addressing (read per launch: A/B)
-  const char* e = getenv("DGVCC_WG9_INC");
-  return !(e && e[0] == '0');
-}
-
-static int wg9_sched() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DGVCC_WG9_SCH");
-    v = (e && e[0] == '0') ? 0 : 2;
-  }
-  return v;
-}
-
-static bool wg9_khalf() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DGVCC_WG9_KH");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-static bool wg9_wide() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DGVCC_WG9_TILE");
-    v = (e && e[0] == '0') ? 0 : 1;  // default: the 64 co x 16 c wave tile (A/B: +2% on the 128-co layers)
-  }
-  return v == 1;
-}
-
 static bool wg9_ok(int C, int Cout, int R, int S, int W, int pad) {
-  return use_pipe() && R == 3 && S == 3 && pad == 1 && W % 64 == 0 && C % 64 == 0 && Cout % 64 == 0;
+  return R == 3 && S == 3 && pad == 1 && W % 64 == 0 && C % 64 == 0 && Cout % 64 == 0;
 }
 
 // the padded-K variant: any W; whole-tensor buffer descriptors (32-bit byte offsets)
@@ -5306,7 +4916,7 @@ static bool wg9p_ok(int N, int H, int W, int C, int Cout, int R, int S, int pad,
   const char* e = getenv("DGVCC_WG9_PAD");
   if (e && e[0] == '0') return false;
   const long long M = (long long)N * H * W;
-  return use_pipe() && R == 3 && S == 3 && pad == 1 && W % 64 != 0 && C % 64 == 0 && Cout % 64 == 0 &&
+  return R == 3 && S == 3 && pad == 1 && W % 64 != 0 && C % 64 == 0 && Cout % 64 == 0 &&
          M * std::max(ldx, lddy) * 2 < (1ll << 31) && (long long)N * (H + 2) * (W + 2) < (1ll << 30);
 }
 
@@ -5407,48 +5017,14 @@ int launch_wgrad(WgArgs a, float* dw, int accumulate, hipStream_t st, unsigned* 
     if (w9 || w9p) {
       const int b9 = a.Cout % 128 == 0 ? 128 : 64;
       const dim3 g9((a.Cout / b9) * (a.C / 64) * a.splits);
-      const int sch = wg9_sched();
-      const bool kh2 = b9 == 64 && sch == 2 && wg9_khalf();
-      if (kh2) slab_splits = 2 * a.splits;  // one slab split per k-half
+      if (b9 == 64) slab_splits = 2 * a.splits;  // one slab split per k-half
       if (w9) {
-        const bool inc = wg9_inc();
-        {
-          const int b = wg9_band_of(a.N, a.H, a.W, a.C);
-          a.band = (inc && b && a.pps % ((long long)b * a.W) == 0) ? b : 0;
-        }
-        if (b9 == 128 && wg9_wide() && sch == 2) {
-          if (inc) hipLaunchKernelGGL((conv_wgrad9_kernel<128, 1, 0, 2, T>), g9, dim3(512), 0, st, a);
-          else hipLaunchKernelGGL((conv_wgrad9_kernel<128, 1, 0, 2, T, 0>), g9, dim3(512), 0, st, a);
-        } else if (b9 == 128 && wg9_wide()) hipLaunchKernelGGL((conv_wgrad9_kernel<128, 1, 0, 0, T, 0>), g9, dim3(512), 0, st, a);
-        else if (b9 == 128) hipLaunchKernelGGL((conv_wgrad9_kernel<128, 0, 0, 0, T, 0>), g9, dim3(512), 0, st, a);
-        else if (kh2) {
-          if (inc) hipLaunchKernelGGL((conv_wgrad9_kernel<64, 2, 0, 2, T>), g9, dim3(512), 0, st, a);
-          else hipLaunchKernelGGL((conv_wgrad9_kernel<64, 2, 0, 2, T, 0>), g9, dim3(512), 0, st, a);
-        } else if (sch == 2) hipLaunchKernelGGL((conv_wgrad9_kernel<64, 0, 0, 2, T, 0>), g9, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((conv_wgrad9_kernel<64, 0, 0, 0, T, 0>), g9, dim3(512), 0, st, a);
-      } else {
-        if (b9 == 128 && wg9_wide() && sch == 2) hipLaunchKernelGGL((conv_wgrad9_kernel<128, 1, 1, 2, T>), g9, dim3(512), 0, st, a);
-        else if (b9 == 128 && wg9_wide()) hipLaunchKernelGGL((conv_wgrad9_kernel<128, 1, 1, 0, T>), g9, dim3(512), 0, st, a);
-        else if (b9 == 128) hipLaunchKernelGGL((conv_wgrad9_kernel<128, 0, 1, 0, T>), g9, dim3(512), 0, st, a);
-        else if (kh2) hipLaunchKernelGGL((conv_wgrad9_kernel<64, 2, 1, 2, T>), g9, dim3(512), 0, st, a);
-        else if (sch == 2) hipLaunchKernelGGL((conv_wgrad9_kernel<64, 0, 1, 2, T>), g9, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((conv_wgrad9_kernel<64, 0, 1, 0, T>), g9, dim3(512), 0, st, a);
-      }
-      done = true;
-    } else if (use_wgrad_pipe()) {  // opt-in: measured slower than the register-staged kernel (round 1)
-      const int RS = a.R * a.S;
-      if (bco == 128 && a.C % 256 == 0) {
-        hipLaunchKernelGGL((conv_wgrad_pipe_kernel<128, 256, T>), dim3((a.Cout / 128) * (a.C / 256) * RS * a.splits),
-                           dim3(512), 0, st, a);
-      } else if (bco == 128 && bc == 128) {
-        hipLaunchKernelGGL((conv_wgrad_pipe_kernel<128, 128, T>), grid, dim3(512), 0, st, a);
-      } else if (bco == 128) {
-        hipLaunchKernelGGL((conv_wgrad_pipe_kernel<128, 64, T>), grid, dim3(512), 0, st, a);
-      } else if (bc == 128) {
-        hipLaunchKernelGGL((conv_wgrad_pipe_kernel<64, 128, T>), grid, dim3(512), 0, st, a);
-      } else {
-        hipLaunchKernelGGL((conv_wgrad_pipe_kernel<64, 64, T>), grid, dim3(512), 0, st, a);
-      }
+        const int b = wg9_band_of(a.N, a.H, a.W, a.C);
+        a.band = (b && a.pps % ((long long)b * a.W) == 0) ? b : 0;
+        if (b9 == 128) hipLaunchKernelGGL((conv_wgrad9_kernel<128, 0, T>), g9, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((conv_wgrad9_kernel<64, 0, T>), g9, dim3(512), 0, st, a);
+      } else if (b9 == 128) hipLaunchKernelGGL((conv_wgrad9_kernel<128, 1, T>), g9, dim3(512), 0, st, a);
+      else hipLaunchKernelGGL((conv_wgrad9_kernel<64, 1, T>), g9, dim3(512), 0, st, a);
       done = true;
     }
   }
@@ -5456,7 +5032,7 @@ int launch_wgrad(WgArgs a, float* dw, int accumulate, hipStream_t st, unsigned* 
   } else if constexpr (!Is16<T>::value) {
     const long long M3 = (long long)a.N * a.P * a.Q;
     const int b3 = wgs3_tile(a.C, a.Cout, a.R, a.S, a.W);
-    const bool nr3 = wgs9_on(b3);
+    const bool nr3 = b3 == 64;
     if (f32_split() && a.stride == 1 && !a.whole_x && a.pad == 1 && b3) {
       const WgPlan p = nr3 ? wgs_plan(M3, wgs9_tiles(a.C, a.Cout), 256) : wgs_plan(M3, wgs3_tiles(a.C, a.Cout, b3), wgs3_slots(b3));
       if ((long long)(p.pps + 2 * (a.W + 1)) * std::max(a.ldx, a.lddy) * 4 < (1ll << 31)) {
@@ -5479,21 +5055,10 @@ int launch_wgrad(WgArgs a, float* dw, int accumulate, hipStream_t st, unsigned* 
           }
         }
         if (h16) {
-          if (nr3) hipLaunchKernelGGL((conv_wgrad_split3_kernel<64, 64, 2, 512, 2, 3, 1>), g3, dim3(512), 0, st, a);
-          else if (b3 == 64) hipLaunchKernelGGL((conv_wgrad_split3_kernel<64, 64, 2, 256, 0, 1, 1>), g3, dim3(256), 0, st, a);
-          else hipLaunchKernelGGL((conv_wgrad_split3_kernel<128, 128, 2, 512, 2, 1, 1>), g3, dim3(512), 0, st, a);
-        } else if (nr3) hipLaunchKernelGGL((conv_wgrad_split3_kernel<64, 64, 2, 512, 2, 3>), g3, dim3(512), 0, st, a);
-        else if (b3 == 64) hipLaunchKernelGGL((conv_wgrad_split3_kernel<64, 64, 2, 256>), g3, dim3(256), 0, st, a);
-        else {
-          // placement of the next step's split + LDS stores among the taps' MFMA blocks: 0 after tap 1,
-          // 1 dY after tap 0 / X after tap 1, 2 (default) all after tap 0: wgrad 0.59 -> 0.60 of the
-          // ceiling (profiles/round2g/wgrad3_swp_ab.txt)
-          const char* e = getenv("DGVCC_WG3_SWP");
-          const int sw = e ? e[0] - '0' : 2;
-          if (sw == 1) hipLaunchKernelGGL((conv_wgrad_split3_kernel<128, 128, 2, 512, 1>), g3, dim3(512), 0, st, a);
-          else if (sw == 2) hipLaunchKernelGGL((conv_wgrad_split3_kernel<128, 128, 2, 512, 2>), g3, dim3(512), 0, st, a);
-          else hipLaunchKernelGGL((conv_wgrad_split3_kernel<128, 128, 2, 512>), g3, dim3(512), 0, st, a);
-        }
+          if (nr3) hipLaunchKernelGGL((conv_wgrad_split3_kernel<64, 64, 3, 1>), g3, dim3(512), 0, st, a);
+          else hipLaunchKernelGGL((conv_wgrad_split3_kernel<128, 128, 1, 1>), g3, dim3(512), 0, st, a);
+        } else if (nr3) hipLaunchKernelGGL((conv_wgrad_split3_kernel<64, 64, 3>), g3, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((conv_wgrad_split3_kernel<128, 128, 1>), g3, dim3(512), 0, st, a);
         done = true;
       }
     }
@@ -5800,7 +5365,7 @@ extern "C" int dg_conv_fwd(int dtype, const void* x, int64_t ldx, int N, int H, 
 // Which forward kernel serves this shape (bf16): 1 = pipelined / fused 3-tap (epilogue
 // statistics available), 0 = register-staged.
 static bool fwd_has_epi_stats(int C, int Cout, long long ldx, int R, int S) {
-  return use_pipe() && C % 64 == 0 && ldx % 8 == 0 && (long long)Cout * R * S * C * 2 < (1ll << 31);
+  return C % 64 == 0 && ldx % 8 == 0 && (long long)Cout * R * S * C * 2 < (1ll << 31);
 }
 
 extern "C" int64_t dg_conv_stats_rows(int N, int H, int W) {
@@ -5823,7 +5388,7 @@ extern "C" int64_t dg_conv_bnpart_rows_ex(int dtype, int N, int H, int W, int C,
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0 || R <= 0 || S <= 0) return DG_ERR_INVALID;
   const long long M = (long long)N * H * W;
   FwdArgs a{nullptr, ldx, N, H, W, C, nullptr, Cout, R, S, (R - 1) / 2, nullptr, nullptr, Cout, 0};
-  if (dtype == DG_F32 && psplit_ok(a)) return dg_cdiv(M, psplit_psb(f32_pers_bn(Cout), psplit_wide()));
+  if (dtype == DG_F32 && psplit_ok(a)) return dg_cdiv(M, psplit_psb(conv_bn(Cout)));
   return dg_cdiv(M, 256);
 }
 extern "C" int dg_conv_fwd_stats(int dtype, const void* x, int64_t ldx, int N, int H, int W, int C, const void* w,
@@ -5852,7 +5417,7 @@ extern "C" int64_t dg_conv_fwd_workspace(int dtype, int N, int H, int W, int C, 
     // room only where the launch takes the pre-split operand (psplit_xs with the shape's tile: several
     // output-channel tiles share a pixel tile of a 3x3 conv; DGVCC_PSPLIT_XS is read here too): a
     // launch given less room splits in-kernel (bit-identical), so a cached size stays safe
-    if (2 * a.pad == R - 1 && 2 * a.pad == S - 1 && psplit_ok(a) && psplit_xs(a, f32_pers_bn(Cout)))
+    if (2 * a.pad == R - 1 && 2 * a.pad == S - 1 && psplit_ok(a) && psplit_xs(a, conv_bn(Cout)))
       return xsplit_off(planes) + xsplit_bytes(a);
     return planes;
   }
@@ -6093,7 +5658,7 @@ extern "C" int64_t dg_conv_wgrad_workspace(int dtype, int N, int H, int W, int C
     const WgPlan q3 = wgs_plan((long long)N * H * W, wgs3_tiles(C, Cout, b3), wgs3_slots(b3));
     if (q3.splits > q.splits) q = q3;
     const WgPlan q9 = wgs_plan((long long)N * H * W, wgs9_tiles(C, Cout), 256);
-    if (wgs9_on(b3) && q9.splits > q.splits) q = q9;
+    if (b3 == 64 && q9.splits > q.splits) q = q9;
   }
   const int kh = (DG_IS16(dtype) && Cout % 128 != 0) ? 2 : 1;  // 9-tap Cout-64 kernel: a slab split per k-half
   // f32: + the f16 x3 operand maxima the library computes when the caller has none (dg_conv_wgrad):

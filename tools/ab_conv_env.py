@@ -1,4 +1,4 @@
-"""Same-process A/B of a conv-forward environment switch read per launch (e.g. DGVCC_PSPLIT_INC,
+"""Same-process A/B of a conv-forward environment switch read per launch (e.g. DGVCC_PSPLIT_XS,
 DGVCC_CONV_KORDER) on the sta_final layer shapes, f32 split math (the pre-split kernel serves
 forward- and dgrad-shaped launches alike), interleaved rounds, min over rounds.  Prints the max
 abs difference between the two arms' outputs (0 when the switch only changes scheduling).
