@@ -82,6 +82,41 @@ class RawDenClsBatch:
     params: torch.Tensor
     points: tuple
     dmaps: torch.Tensor | None = None
+    # DenClsDataset(bl_targets=True): per image, every annotation in crop coordinates before the
+    # in-crop mask and the flip (f32 [n, 2]), and st_size [B] (datasets/bay_dataset.py:69-71)
+    all_points: tuple | None = None
+    st_sizes: torch.Tensor | None = None
+
+
+class GtDatas(tuple):
+    """The reference's `(points, dmaps, bmaps)` (indexing, [-1] and 3-way unpacking as a plain
+    tuple) that also carries the Bayesian-loss batch: `bl = (points_kept, targets, st_sizes)`."""
+    bl = None
+
+    def __new__(cls, items, bl=None):
+        self = super().__new__(cls, items)
+        self.bl = bl
+        return self
+
+
+def bl_batch(all_points, st_sizes, params: torch.Tensor, h: int, w: int, device):
+    """(points_kept, targets, st_sizes) of a batch for losses.bl.BL: the per-point targets of
+    the reference's BayesianDataset computed on `device` (dg_bl_targets) from the unfiltered
+    annotations; x is mirrored where the record's flip flag is set.  params: the [B,16] records
+    on `device`.  One device-to-host copy (the B+1 offsets of the kept points) splits the lists."""
+    counts = [int(p.shape[0]) for p in all_points]
+    B = len(counts)
+    offs = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int64).to(device, non_blocking=True)
+    if sum(counts):
+        pts = torch.cat([p.reshape(-1, 2) for p in all_points]).to(device=device, dtype=torch.float32,
+                                                                  non_blocking=True).contiguous()
+    else:
+        pts = torch.empty((0, 2), dtype=torch.float32, device=device)
+    kept, targets, koffs = K.bl_targets(pts, offs, h, w, params[:, P["flip"]:P["flip"] + 1])
+    ko = koffs.cpu().tolist()
+    points_kept = tuple(kept[ko[b]:ko[b + 1]] for b in range(B))
+    targets = tuple(targets[ko[b]:ko[b + 1]] for b in range(B))
+    return points_kept, targets, torch.as_tensor(st_sizes, dtype=torch.float32).to(device, non_blocking=True)
 
 
 def augment_den_cls(imgs: torch.Tensor, params: torch.Tensor):
@@ -118,12 +153,19 @@ class DeviceAugment:
 
     def __call__(self, raw: RawDenClsBatch):
         imgs = raw.imgs.to(self.device, non_blocking=True)
-        img1, img2 = augment_den_cls(imgs, raw.params)
+        params = raw.params.to(device=self.device, dtype=torch.float32).contiguous()
+        img1, img2 = augment_den_cls(imgs, params)
         dmaps = raw.dmaps.to(self.device, non_blocking=True)
         bmaps = block_map(dmaps)
-        return img1, img2, (tuple(p.to(self.device) for p in raw.points), dmaps, bmaps)
+        gt_datas = (tuple(p.to(self.device) for p in raw.points), dmaps, bmaps)
+        if raw.all_points is None:
+            return img1, img2, gt_datas
+        if raw.st_sizes is None:
+            raise ValueError("a batch with all_points needs st_sizes")
+        bl = bl_batch(raw.all_points, raw.st_sizes, params, imgs.shape[1], imgs.shape[2], self.device)
+        return img1, img2, GtDatas(gt_datas, bl)
 
 
-__all__ = ["AUG_PARAMS", "RawDenClsBatch", "DeviceAugment", "augment_den_cls", "block_map", "draw_more_transform",
+__all__ = ["AUG_PARAMS", "RawDenClsBatch", "DeviceAugment", "GtDatas", "bl_batch", "augment_den_cls", "block_map", "draw_more_transform",
            "new_record", "hue_shift", "gaussian_weights"]
 _ = K  # the kernels module loads the library (fails loudly when it is missing)

@@ -35,7 +35,7 @@ class DenClsDataset(torch.utils.data.Dataset):
     """reference datasets/den_cls_dataset.py:16-186 (constructor arguments as the reference)."""
 
     def __init__(self, root, crop_size, downsample, method, is_grey=False, unit_size=0, pre_resize=1,
-                 roi_map_path=None, gt_dir=None, gen_root=None):
+                 roi_map_path=None, gt_dir=None, gen_root=None, bl_targets=False):
         self.root = root
         self.gen_root = gen_root
         self.crop_size = (crop_size, crop_size) if isinstance(crop_size, int) else tuple(crop_size)
@@ -45,6 +45,7 @@ class DenClsDataset(torch.utils.data.Dataset):
         self.unit_size = unit_size
         self.pre_resize = pre_resize
         self.gt_dir = gt_dir
+        self._set_bl_targets(bl_targets)
         # the reference loads the ROI map with allow_pickle=True (base_dataset.py:31); here only
         # plain arrays are accepted
         self.roi_map = _load_array(roi_map_path) if roi_map_path is not None else None
@@ -55,6 +56,15 @@ class DenClsDataset(torch.utils.data.Dataset):
             self.img_fns += glob(os.path.join(gen_root, "*.jpg")) + glob(os.path.join(gen_root, "*.png"))
         if method in ("val", "test"):
             self.img_fns = sorted(self.img_fns)
+
+    def _set_bl_targets(self, flag):
+        """Bayesian-loss training: a training sample also carries every annotation in crop
+        coordinates (unfiltered) and st_size, from which DeviceAugment computes the per-point
+        targets on the GPU (dg_bl_targets)."""
+        self.bl_targets = bool(flag)
+        if self.bl_targets and (self.downsample != 1 or self.crop_size[0] != self.crop_size[1]):
+            raise ValueError(f"bl_targets needs downsample == 1 and a square crop (got downsample "
+                             f"{self.downsample}, crop {self.crop_size})")
 
     def __len__(self):
         return len(self.img_fns)
@@ -125,10 +135,12 @@ class DenClsDataset(torch.utils.data.Dataset):
         dmap = dmap[:, i:i + h, j:j + w]
         if len(gt) > 0:
             gt = gt - [j, i]
+            all_points = gt
             idx_mask = (gt[:, 0] >= 0) * (gt[:, 0] <= w) * (gt[:, 1] >= 0) * (gt[:, 1] <= h)
             gt = gt[idx_mask]
         else:
             gt = np.empty([0, 2])
+            all_points = gt
         ds = self.downsample
         dmap = dmap.reshape([1, h // ds, ds, w // ds, ds]).sum(dim=(2, 4))
         if len(gt) > 0:
@@ -140,8 +152,12 @@ class DenClsDataset(torch.utils.data.Dataset):
                 gt[:, 0] = w - gt[:, 0]
         rec = new_record(grey=grey, flip=flip)
         draw_more_transform(rec)  # torch RNG, as more_transform(img) would consume it
-        return (torch.from_numpy(img), torch.from_numpy(rec), torch.from_numpy(gt.copy()).float(),
-                dmap.float())
+        sample = (torch.from_numpy(img), torch.from_numpy(rec), torch.from_numpy(gt.copy()).float(),
+                  dmap.float())
+        if self.bl_targets:  # datasets/bay_dataset.py:69-71
+            sample += (torch.from_numpy(np.ascontiguousarray(all_points, dtype=np.float32).reshape(-1, 2)),
+                       max(st_size, 1.0 * self.crop_size[0]))
+        return sample
 
     # ---- den_cls_dataset.py:159-185 -----------------------------------------------------
     def _val_transform(self, img, gt, name):
@@ -168,8 +184,13 @@ class DenClsDataset(torch.utils.data.Dataset):
     @staticmethod
     def collate(batch):
         """Training samples -> RawDenClsBatch (the reference's collate after the GPU pass)."""
-        imgs, recs, points, dmaps = zip(*batch)
-        return RawDenClsBatch(torch.stack(imgs, 0), torch.stack(recs, 0), tuple(points), torch.stack(dmaps, 0))
+        cols = list(zip(*batch))
+        imgs, recs, points, dmaps = cols[:4]
+        raw = RawDenClsBatch(torch.stack(imgs, 0), torch.stack(recs, 0), tuple(points), torch.stack(dmaps, 0))
+        if len(cols) > 4:  # bl_targets samples
+            raw.all_points = tuple(cols[4])
+            raw.st_sizes = torch.tensor(cols[5], dtype=torch.float32)
+        return raw
 
 
 def augment_val_sample(sample, device):

@@ -21,7 +21,7 @@ class JHUDomainClsDataset(DenClsDataset):
     unused there too (the split comes from the domain list file)."""
 
     def __init__(self, root, domain_label, crop_size, domain_type, domain, downsample, method, is_grey=False,
-                 unit_size=0, pre_resize=1):
+                 unit_size=0, pre_resize=1, bl_targets=False):
         if method not in ("train", "val", "test"):
             raise ValueError("method must be train, val or test")
         self.root = root
@@ -37,6 +37,7 @@ class JHUDomainClsDataset(DenClsDataset):
         self.pre_resize = pre_resize
         self.gt_dir = None
         self.roi_map = None
+        self._set_bl_targets(bl_targets)
         phase = {"train": "train", "val": "val", "test": "val"}[method]
         with open(os.path.join(root, "domains", f"{domain_label}_{phase}.txt")) as f:
             self.img_fns = [ln.strip() for ln in f.readlines()]

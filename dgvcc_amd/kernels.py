@@ -703,6 +703,55 @@ def mse_loss(pred: torch.Tensor, gt: torch.Tensor, gt_scale: float, want_grad=Tr
     return loss, dpred
 
 
+def bl_targets(points: torch.Tensor, offsets: torch.Tensor, h: int, w: int, flips: torch.Tensor,
+               want_all: bool = False):
+    """Bayesian-loss targets of B crops of h x w (dg_bl_targets).  points f32 [total, 2]: every
+    annotation in crop coordinates, unfiltered; offsets int64 [B+1]; flips f32 [B] or [B, k] (row b's
+    flag at flips[b, 0]; pass a column view such as params[:, 1:] of the augmentation records).
+    Returns (kept points [total, 2], targets [total], new offsets int64 [B+1]), all on device; only
+    the first new_offsets[B] rows of the first two are written.  want_all adds (d, ratio) of every
+    input point.  Stream-ordered, no host synchronisation."""
+    dev = offsets.device
+    total, B = points.shape[0], offsets.numel() - 1
+    if points.dtype != torch.float32 or not points.is_contiguous() or offsets.dtype != torch.int64:
+        raise DGError("bl_targets: points must be contiguous float32 [total, 2], offsets int64 [B+1]")
+    if flips.dtype != torch.float32 or flips.device != dev or flips.shape[0] != B or flips.stride(0) < 1:
+        raise DGError("bl_targets: flips must be a float32 device tensor with one row per image")
+    out_pts = torch.empty((total, 2), dtype=torch.float32, device=dev)
+    out_tg = torch.empty((total,), dtype=torch.float32, device=dev)
+    out_offs = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+    d = torch.empty((total,), dtype=torch.float32, device=dev) if want_all else None
+    ratio = torch.empty((total,), dtype=torch.float32, device=dev) if want_all else None
+    ws = query("dg_bl_targets_workspace", B, total)
+    work = torch.empty(ws // 4, dtype=torch.int32, device=dev)
+    call("dg_bl_targets", ptr(points) if total else None, ptr(offsets), total, B, int(h), int(w), ptr(flips),
+         flips.stride(0), ptr(out_pts) if total else None, ptr(out_tg) if total else None, ptr(out_offs),
+         ptr(d) if total else None, ptr(ratio) if total else None, ptr(work), stream())
+    if want_all:
+        return out_pts, out_tg, out_offs, d, ratio
+    return out_pts, out_tg, out_offs
+
+
+def sum_pool1_fwd(x: torch.Tensor, s: int, scale: float) -> torch.Tensor:
+    """scale * (s x s window sums) of a contiguous f32 [B, H, W] map (dg_sum_pool1_fwd)."""
+    _f32_flat(x, "sum_pool1_fwd")
+    B, H, W = x.shape
+    if H % s or W % s:
+        raise DGError(f"sum_pool1_fwd: {H}x{W} is not a multiple of the window {s}")
+    y = torch.empty((B, H // s, W // s), dtype=torch.float32, device=x.device)
+    call("dg_sum_pool1_fwd", ptr(x), B, H, W, int(s), float(scale), ptr(y), stream())
+    return y
+
+
+def sum_pool1_bwd(gy: torch.Tensor, s: int, scale: float) -> torch.Tensor:
+    """Gradient of sum_pool1_fwd: gy [B, H/s, W/s] -> [B, H, W] (dg_sum_pool1_bwd)."""
+    _f32_flat(gy, "sum_pool1_bwd")
+    B, Ho, Wo = gy.shape
+    gx = torch.empty((B, Ho * s, Wo * s), dtype=torch.float32, device=gy.device)
+    call("dg_sum_pool1_bwd", ptr(gy), B, Ho * s, Wo * s, int(s), float(scale), ptr(gx), stream())
+    return gx
+
+
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, wd, step):
     call("dg_adamw_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(beta1),
          float(beta2), float(eps), float(wd), int(step), stream())

@@ -59,6 +59,35 @@ class _BLFn(torch.autograd.Function):
         return gd, None, None, None, None, None, None
 
 
+class _SumPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, s, scale):
+        from .. import kernels as K
+        ctx.meta = (s, scale, x.shape, x.dtype)
+        B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+        y = K.sum_pool1_fwd(x.float().contiguous().view(B, H, W), s, scale)
+        return y.view(B, 1, H // s, W // s)
+
+    @staticmethod
+    def backward(ctx, gy):
+        from .. import kernels as K
+        s, scale, shape, dtype = ctx.meta
+        gx = K.sum_pool1_bwd(gy.float().contiguous().view(gy.shape[0], gy.shape[-2], gy.shape[-1]), s, scale)
+        return gx.view(shape).to(dtype), None, None
+
+
+def sum_pool(pred: torch.Tensor, stride: int, scale: float = 1.0) -> torch.Tensor:
+    """[B,1,H,W] -> [B,1,H/stride,W/stride]: scale * the stride x stride window sums, on the HIP
+    sum pool (dg_sum_pool1_fwd / _bwd).  Brings a model's full-resolution map in log_para units
+    onto BL's grid in counts: sum_pool(pred, stride, 1 / log_para)."""
+    if pred.dim() != 4 or pred.shape[1] != 1:
+        raise ValueError(f"sum_pool expects [B,1,H,W], got {tuple(pred.shape)}")
+    stride = int(stride)
+    if stride < 1 or pred.shape[-2] % stride or pred.shape[-1] % stride:
+        raise ValueError(f"a {pred.shape[-2]}x{pred.shape[-1]} map does not divide into windows of {stride}")
+    return _SumPoolFn.apply(pred, stride, float(scale))
+
+
 class Post_Prob(Module):
     """Posterior of every grid cell over the annotated points (bl.py:5-52)."""
 

@@ -9,7 +9,8 @@ implementations behind them:
   process group, one GPU per rank, DistributedSampler over the train set, identical initial
   weights (broadcast from rank 0), the flat-gradient all-reduce inside the fused AdamW, and
   logs / checkpoints written by rank 0 only;
-* losses: 'mse' -> the fused HIP MSELoss, 'bl' -> the fused Bayesian loss;
+* losses: 'mse' -> the fused HIP MSELoss, 'bl' -> the fused Bayesian loss (its train set then
+  also delivers the unfiltered annotations; the per-point targets are computed on the GPU);
 * datasets: 'den_cls' and 'jhu_domain_cls' (every shipped config's train/val/test set)
   with the pixel augmentation on the GPU; the other reference datasets ('den', 'bay',
   'jhu_domain') are not on the hot path (SURVEY.md §8) and raise;
@@ -95,6 +96,23 @@ def get_scheduler(name, params, optimizer):
     return table[name](optimizer, **params)
 
 
+def _bl_train_params(cfg):
+    """The train set's parameters.  With `loss: bl` on 'den_cls' / 'jhu_domain_cls' the train set
+    (only) also delivers what the Bayesian loss needs (`bl_targets=True`), and the loss's grid
+    must tile the crop: c_size == crop_size, c_size % stride == 0 (checked before any data is read)."""
+    params = cfg["train_dataset"]["params"]
+    if cfg["loss"]["name"] != "bl" or cfg["train_dataset"]["name"] not in ("den_cls", "jhu_domain_cls"):
+        return params
+    lp = cfg["loss"]["params"]
+    crop = params["crop_size"]
+    crop = (crop, crop) if isinstance(crop, int) else tuple(crop)
+    if crop[0] != crop[1] or lp["c_size"] != crop[0]:
+        raise ValueError(f"loss bl: c_size {lp['c_size']} must equal the train set's (square) crop_size {crop}")
+    if lp["c_size"] % lp["stride"] != 0:
+        raise ValueError(f"loss bl: c_size {lp['c_size']} is not a multiple of stride {lp['stride']}")
+    return dict(params, bl_targets=True)
+
+
 def load_config(config_path, task):
     """(init_params, task_params) exactly as main.py:102-136."""
     with open(config_path) as f:
@@ -111,8 +129,9 @@ def load_config(config_path, task):
                    "checkpoint": cfg["checkpoint"]}
     generator = get_seeded_generator(cfg["seed"])
     if task in ("train", "train_test"):
+        train_params = _bl_train_params(cfg)
         task_params["loss"] = get_loss(cfg["loss"]["name"], cfg["loss"]["params"])
-        train_set, collate = get_dataset(cfg["train_dataset"]["name"], cfg["train_dataset"]["params"], "train")
+        train_set, collate = get_dataset(cfg["train_dataset"]["name"], train_params, "train")
         loader_kw = dict(cfg["train_loader"])
         if D.world() > 1:
             # frames shard over ranks: each rank reads its 1/world of every

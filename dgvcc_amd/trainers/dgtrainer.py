@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from ..losses import mse_loss
 from ..losses.bce import binary_cross_entropy
+from ..losses.bl import sum_pool
 from ..utils.misc import denormalize, divide_img_into_patches
 from .trainer import Trainer
 
@@ -55,6 +56,15 @@ class DGTrainer(Trainer):
                 gt_dmaps = gt_dmaps * weights
             return mse_loss(pred_dmaps, gt_dmaps, self.log_para)
         if name == "BL":
+            if getattr(gt_datas, "bl", None) is not None:
+                # a DeviceAugment batch: the targets were computed on the device; the model's
+                # full-resolution map in log_para units is pooled onto the loss's grid in counts
+                gts, targs, st_sizes = gt_datas.bl
+                stride, G = int(loss.cfg["stride"]), loss.G
+                if pred_dmaps.shape[-2] != G * stride or pred_dmaps.shape[-1] != G * stride:
+                    raise ValueError(f"BL expects a {G * stride}x{G * stride} prediction (grid {G} x stride "
+                                     f"{stride}), got {pred_dmaps.shape[-2]}x{pred_dmaps.shape[-1]}")
+                return loss(gts, st_sizes, targs, sum_pool(pred_dmaps.float(), stride, 1.0 / self.log_para))
             gts, targs, st_sizes = gt_datas
             gts = [g.to(self.device) for g in gts]
             targs = [t.to(self.device) for t in targs]

@@ -685,6 +685,27 @@ int dg_bl_loss(const float* points, const int64_t* offsets, int64_t total_points
 int dg_bl_prob(const float* points, const int64_t* offsets, int64_t total_points,
                const float* st_sizes, int B, int G, float stride, float sigma, float bg_ratio,
                int use_bg, const int64_t* row_offsets, float* prob, void* workspace, void* stream);
+/* The per-point targets that loss trains on (datasets/bay_dataset.py:38-48, 85-98), for B crops of
+ * h x w.  points [total][2] (x, y): every annotation of the padded source image in crop
+ * coordinates, unfiltered, concatenated with offsets[B+1] (device int64).  Per image with n points:
+ * d_i = 4 for n = 1; the mean of the 2nd..4th smallest distances of point i (itself included: its 0
+ * and those of duplicates count) for n >= 4; the mean of dist(i, k), k = 1..n-1 by index for
+ * n = 2, 3 (the reference's dists[:, 1:]).  f32, sqrtf(dx*dx + dy*dy).  s = clip(d, 4, 128),
+ * ratio = clip(area((p +- s/2) ^ [0,w] x [0,h]) / s^2, 0, 1); points with ratio >= 0.3 are kept in
+ * their order: out_points [<= total][2] (x -> w - x where flips[b * flip_stride] != 0, e.g. the
+ * flip column of the augmentation records), out_targets = their ratios, out_offsets[B+1].
+ * dist_out / ratio_out (each [total], may be NULL): the unclipped d and the ratio of every input
+ * point.  Deterministic (no atomics); workspace: dg_bl_targets_workspace(B, total) bytes. */
+int64_t dg_bl_targets_workspace(int B, int64_t total_points);
+int dg_bl_targets(const float* points, const int64_t* offsets, int64_t total_points, int B, int h,
+                  int w, const float* flips, int flip_stride, float* out_points, float* out_targets,
+                  int64_t* out_offsets, float* dist_out, float* ratio_out, void* workspace,
+                  void* stream);
+/* Strided sum pool of a one-channel f32 map: y[b][i][j] = scale * sum of the s x s window of
+ * x [B][H][W] (rows left to right, then top to bottom: a fixed order); H % s == 0 and W % s == 0,
+ * else DG_ERR_UNSUPPORTED.  Backward: gx[b][u][v] = scale * gy[b][u/s][v/s]. */
+int dg_sum_pool1_fwd(const float* x, int B, int H, int W, int s, float scale, float* y, void* stream);
+int dg_sum_pool1_bwd(const float* gy, int B, int H, int W, int s, float scale, float* gx, void* stream);
 
 /* ---- optimizer -----------------------------------------------------------------
  * torch.optim.AdamW step over one flat f32 buffer (main.py:85-86). */
