@@ -106,16 +106,42 @@ def _ident_stats(C, dev):
     return st
 
 
+def phase_mask(drop: torch.Tensor | None, d: int) -> torch.Tensor | None:
+    """A per-image [N, C] channel mask for the [N d^2, ...] phase batch: every phase of an image
+    shares its image's row (phase b belongs to image b // d^2)."""
+    if drop is None or d == 1:
+        return drop
+    return drop.repeat_interleave(d * d, dim=0)
+
+
 class ConvLayer:
-    """Conv2d(k in {1,3}, stride 1, same pad) [+ BatchNorm2d] [+ ReLU] [+ channel mask]."""
+    """Conv2d(k in {1,3}, stride 1, same pad) [+ BatchNorm2d] [+ ReLU] [+ channel mask].
+
+    A 3x3 conv with dilation (d, d) and padding (d, d) runs as the dense pad-1 layer on the d*d phase
+    sub-images of its input: in image-layout mode (the default) forward / backward
+    wrap the dense launches in dg_space_to_batch / dg_batch_to_space; with `resident` set (by a plan
+    that keeps a run of such layers in phase layout) input and output already are phase batches
+    and the layer is the dense layer."""
 
     def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d | None, act: int = ACT_RELU,
                  first: bool = False):
-        assert conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
+        self.dil = 1
+        if tuple(conv.dilation) != (1, 1):
+            d = conv.dilation[0]
+            if (tuple(conv.dilation) != (d, d) or tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1)
+                    or conv.padding != (d, d) or conv.groups != 1 or first):
+                raise ValueError(
+                    "ConvLayer: a dilated convolution is supported as kernel_size (3, 3), stride (1, 1), "
+                    f"dilation (d, d), padding (d, d), groups 1 behind an NHWC input; got kernel_size="
+                    f"{tuple(conv.kernel_size)}, stride={tuple(conv.stride)}, dilation={tuple(conv.dilation)}, "
+                    f"padding={conv.padding}, groups={conv.groups}{', first layer' if first else ''}")
+            self.dil = d
+        assert conv.stride == (1, 1) and conv.groups == 1
         self.conv, self.bn, self.act, self.first = conv, bn, act, first
         self.scope = "head"  # FeaturePlan relabels its encoder / decoder layers (bench timing)
         self.R = conv.kernel_size[0]
-        self.pad = conv.padding[0]
+        self.pad = conv.padding[0] if self.dil == 1 else 1  # of the dense conv the kernels run
+        self.resident = False
         self.Cin, self.Cout = conv.in_channels, conv.out_channels
         # the output (pooled output when pooling) is the input of a conv forward (FeaturePlan sets it):
         # the fp32 training BN apply then writes that conv's pair image (_BN_PAIR)
@@ -154,6 +180,32 @@ class ConvLayer:
 
     def forward(self, x, out: Act | None, training: bool, tape: dict | None,
                 drop: torch.Tensor | None = None, pool: Act | None = None):
+        if self.dil == 1 or self.resident:
+            return self._forward(x, out, training, tape, drop=drop, pool=pool)
+        # image-layout mode of a dilated layer: phase batch in, dense layer, image batch out.  The tape
+        # holds the phase-layout tensors; drop is the per-image [N, C] mask.
+        d = self.dil
+        if pool is not None or out is None or not isinstance(x, Act):
+            raise ValueError("ConvLayer: a dilated layer reads an NHWC activation and writes an un-pooled output")
+        if (out.N, out.H, out.W) != (x.N, x.H, x.W) or out.C != self.Cout or x.C != self.Cin:
+            raise ValueError(f"ConvLayer: output {(out.N, out.H, out.W, out.C)} != input "
+                             f"{(x.N, x.H, x.W)} x Cout {self.Cout} (Cin {self.Cin}, got {x.C})")
+        if training and self.bn is not None and (x.H % d or x.W % d):
+            # the zero-filled border of a ragged phase would enter the batch statistics
+            raise ValueError(f"ConvLayer: a dilated layer with BatchNorm batch statistics needs H and W "
+                             f"divisible by the dilation {d} (got {x.H}x{x.W})")
+        dt, dev = out.buf.dtype, out.buf.device
+        Np, Hp, Wp = K.phase_shape(x.N, x.H, x.W, d)
+        xs = Act(K.nhwc(Np, Hp, Wp, self.Cin, dt, dev))
+        K.space_to_batch(x, d, xs)
+        ys = Act(K.nhwc(Np, Hp, Wp, self.Cout, dt, dev))
+        self._forward(xs, ys, training, tape, drop=phase_mask(drop, d))
+        K.batch_to_space(ys, d, out)
+        if tape is not None:
+            tape[("phases", self)] = (x.N, x.H, x.W)
+
+    def _forward(self, x, out: Act | None, training: bool, tape: dict | None,
+                 drop: torch.Tensor | None = None, pool: Act | None = None):
         """x: NHWC Act, or for the fused bf16 stem the NCHW f32 image itself.
         pool: also apply the following MaxPool2d(2,2) into `pool` (BN/ReLU/pool in one pass);
         `out` (the un-pooled activation) may then be None when nothing else reads it."""
@@ -273,6 +325,31 @@ class ConvLayer:
 
     def backward(self, tape: dict, g: Act | None, gx: Act | None, accumulate_gx: bool = False,
                  g_pool: Act | None = None, gx_bn: "ConvLayer | None" = None) -> dict:
+        shape = tape.pop(("phases", self), None)
+        if shape is None:
+            return self._backward(tape, g, gx, accumulate_gx=accumulate_gx, g_pool=g_pool, gx_bn=gx_bn)
+        # the forward ran in image-layout mode: g's phase batch, the dense backward, gx's image batch
+        # (each layout pass is the other's adjoint)
+        d = self.dil
+        if g is None or g_pool is not None:
+            raise ValueError("ConvLayer: a dilated layer takes the gradient of its un-pooled output")
+        if (g.N, g.H, g.W) != shape or g.C != self.Cout:
+            raise ValueError(f"ConvLayer: gradient {(g.N, g.H, g.W, g.C)} != forward output {shape + (self.Cout,)}")
+        if gx is not None and ((gx.N, gx.H, gx.W) != shape or gx.C != self.Cin):
+            raise ValueError(f"ConvLayer: input gradient {(gx.N, gx.H, gx.W, gx.C)} != forward input "
+                             f"{shape + (self.Cin,)}")
+        dt, dev = g.buf.dtype, g.buf.device
+        Np, Hp, Wp = K.phase_shape(*shape, d)
+        gs = Act(K.nhwc(Np, Hp, Wp, self.Cout, dt, dev))
+        K.space_to_batch(g, d, gs)
+        gxs = Act(K.nhwc(Np, Hp, Wp, self.Cin, dt, dev)) if gx is not None else None
+        grads = self._backward(tape, gs, gxs)
+        if gx is not None:
+            K.batch_to_space(gxs, d, gx, accumulate=accumulate_gx)
+        return grads
+
+    def _backward(self, tape: dict, g: Act | None, gx: Act | None, accumulate_gx: bool = False,
+                  g_pool: Act | None = None, gx_bn: "ConvLayer | None" = None) -> dict:
         """g: gradient of the layer output (None if only the pooled output was used);
         g_pool: gradient of the pooled output when the forward ran with `pool`;
         gx_bn: the layer whose whole output gradient gx is (its BN-backward partial sums

@@ -671,6 +671,41 @@ def upsample_bwd(gy: Act, scale: int, mode: int, gx: Act, gy2: Act | None = None
     gx.amax = None
 
 
+def phase_shape(N: int, H: int, W: int, d: int) -> tuple[int, int, int]:
+    """(N d^2, ceil(H/d), ceil(W/d)): the phase batch of an [N, H, W] image batch at dilation d."""
+    return N * d * d, -(-H // d), -(-W // d)
+
+
+def _phase_guard(img: Act, ph: Act, d: int, what: str):
+    if d < 1:
+        raise DGError(f"{what}: dilation {d} < 1")
+    if (ph.N, ph.H, ph.W) != phase_shape(img.N, img.H, img.W, d) or ph.C != img.C:
+        raise DGError(f"{what}: phase batch {(ph.N, ph.H, ph.W, ph.C)} != "
+                      f"{phase_shape(img.N, img.H, img.W, d) + (img.C,)} of the image batch "
+                      f"{(img.N, img.H, img.W, img.C)} at d = {d}")
+    if img.buf.dtype != ph.buf.dtype:
+        raise DGError(f"{what}: dtypes differ ({img.buf.dtype} vs {ph.buf.dtype})")
+
+
+def space_to_batch(x: Act, d: int, y: Act, accumulate=False):
+    """y [N d^2, Hp, Wp, C] (+)= the d x d phase sub-images of x [N, H, W, C], zero outside the image
+    (dg_space_to_batch); the adjoint of batch_to_space."""
+    _phase_guard(x, y, d, "space_to_batch")
+    call("dg_space_to_batch", x.dt, x.ptr, x.ld, x.N, x.H, x.W, x.C, d, y.ptr, y.ld, int(accumulate), stream())
+    # a permutation with zero fill never raises a channel's max |.| (an accumulated sum may)
+    y.amax = None if accumulate else x.amax
+    y.pair = None
+
+
+def batch_to_space(x: Act, d: int, y: Act, accumulate=False):
+    """y [N, H, W, C] (+)= the image batch of the phase batch x [N d^2, Hp, Wp, C], cropped to H x W
+    (dg_batch_to_space); the adjoint of space_to_batch."""
+    _phase_guard(y, x, d, "batch_to_space")
+    call("dg_batch_to_space", x.dt, x.ptr, x.ld, y.N, y.H, y.W, x.C, d, y.ptr, y.ld, int(accumulate), stream())
+    y.amax = None if accumulate else x.amax
+    y.pair = None
+
+
 # ---------------------------------------------------------------- head -----
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 

@@ -23,13 +23,20 @@ class ChainPlan:
     as its channel mask (F.dropout2d order: act, then mask); MaxPool2d(2) and bilinear
     Upsample(x2); a final 1x1 ConvBlock with <= 4 output channels and no BN is the terminal
     head (one dg_head_fwd per output channel, ReLU / Sigmoid / none) and a trailing nn.Tanh
-    runs dg_tanh_fwd on it.  cat_input: the first op is the 1x1 conv on the decoder
+    runs dg_tanh_fwd on it; a bare terminal nn.Conv2d(C, k <= 4, 1) is such a head too (CSRNet's
+    output_layer).  A maximal run of consecutive convs with the same dilation d > 1 stays in phase
+    layout (one dg_space_to_batch before it, one dg_batch_to_space after it) when the run's input has
+    H % d == 0 and W % d == 0, decided per call; otherwise each dilated layer converts by itself
+    (DESIGN.md §3.3).  cat_input: the first op is the 1x1 conv on the decoder
     concatenation parts (engine.CatConvLayer); image_input: the first conv reads the NCHW f32
     image through the Cin=3 im2col (engine.ConvLayer first=True)."""
 
     def __init__(self, modules, cat_input: bool = False, image_input: bool = False):
         mods = list(modules)
         self.cat_input, self.image_input = cat_input, image_input
+        # runs of dilated convs stay in phase layout when H and W divide by d (decided per call);
+        # False: every dilated layer converts in and out of image layout itself
+        self.resident = True
         self.ops = []
         self._params = []
         for i, m in enumerate(mods):
@@ -50,6 +57,15 @@ class ChainPlan:
                 act = E.ACT_RELU if m.relu is not None else E.ACT_NONE
                 self._conv(conv, bn, act, nxt)
             elif isinstance(m, nn.Conv2d):
+                if (not rest_has_conv and m.kernel_size == (1, 1) and m.out_channels <= 4 and self.ops
+                        and m.stride == (1, 1) and m.padding == (0, 0) and m.groups == 1):
+                    # a bare 1x1 terminal conv (CSRNet's output_layer) is a head as the ConvBlock one
+                    act = K.ACT_RELU if isinstance(nxt, nn.ReLU) else K.ACT_NONE
+                    if isinstance(nxt, nn.Sigmoid):
+                        act = K.ACT_SIGMOID
+                    self.ops.append(["head", m, act, isinstance(nxt, nn.Tanh)])
+                    self._params += [m.weight] + ([m.bias] if m.bias is not None else [])
+                    continue
                 self._conv(m, None, E.ACT_RELU if isinstance(nxt, nn.ReLU) else E.ACT_NONE, None)
             elif isinstance(m, nn.MaxPool2d):
                 if m.kernel_size not in (2, (2, 2)) or m.stride not in (2, (2, 2)):
@@ -79,6 +95,13 @@ class ChainPlan:
     def params(self):
         return self._params
 
+    def _run_end(self, i: int) -> int:
+        """Last op of the maximal run of consecutive conv ops with op i's dilation."""
+        d, j = self.ops[i][1].dil, i
+        while j + 1 < len(self.ops) and self.ops[j + 1][0] == "conv" and self.ops[j + 1][1].dil == d:
+            j += 1
+        return j
+
     # ----------------------------------------------------------------- forward --
     def run(self, x, dt, training: bool, tape: dict | None, out: Act | None = None):
         """x: NCHW image (image_input), CatParts (cat_input) or an NHWC Act.  out: where the
@@ -88,16 +111,36 @@ class ChainPlan:
             x = Act(K.im2col_c3(x.float().contiguous(), dt))
         rec = []
         nops = len(self.ops)
+        run_d, run_end, img = 1, -1, None  # inside a phase-resident run: its d, last op, image (N, H, W)
         for i, op in enumerate(self.ops):
             kind = op[0]
             if kind == "conv":
                 layer, p = op[1], op[2]
+                x_img = None
+                if layer.dil > 1 and run_d == 1 and self.resident and x.H % layer.dil == 0 and x.W % layer.dil == 0:
+                    # a maximal run of convs with this dilation stays in phase layout: one
+                    # space-to-batch here, one batch-to-space after its last layer
+                    run_d, run_end, img, x_img = layer.dil, self._run_end(i), (x.N, x.H, x.W), x
+                    x = Act(K.nhwc(*K.phase_shape(*img, run_d), x.C, dt, x.buf.device))
+                    K.space_to_batch(x_img, run_d, x)
                 N, H, W = x.N, x.H, x.W
                 dev = x.parts[0].buf.device if isinstance(x, E.CatParts) else x.buf.device
-                y = out if (out is not None and i == nops - 1) else Act(K.nhwc(N, H, W, layer.Cout, dt, dev))
-                drop = E.dropout2d_mask(N, layer.Cout, p, dev) if (training and p > 0) else None
-                layer.forward(x, y, training, tape, drop=drop)
-                rec.append((x, y))
+                closes = run_d > 1 and i == run_end
+                y = out if (out is not None and i == nops - 1 and run_d == 1) \
+                    else Act(K.nhwc(N, H, W, layer.Cout, dt, dev))
+                n_img = img[0] if run_d > 1 else N  # Dropout2d draws one mask row per image
+                drop = E.dropout2d_mask(n_img, layer.Cout, p, dev) if (training and p > 0) else None
+                layer.resident = run_d > 1
+                try:
+                    layer.forward(x, y, training, tape, drop=E.phase_mask(drop, run_d))
+                finally:
+                    layer.resident = False
+                rec.append((x, y, x_img, (run_d, img) if closes else None))
+                if closes:
+                    y_img = out if (out is not None and i == nops - 1) \
+                        else Act(K.nhwc(*img, layer.Cout, dt, dev))
+                    K.batch_to_space(y, run_d, y_img)
+                    y, run_d, img = y_img, 1, None
             elif kind == "pool":
                 y = Act(K.nhwc(x.N, x.H // 2, x.W // 2, x.C, x.buf.dtype, x.buf.device))
                 K.maxpool_fwd(x, y)
@@ -135,6 +178,9 @@ class ChainPlan:
         for i in range(nops - 1, -1, -1):
             op, r = self.ops[i], rec[i]
             x = r[0]
+            opens = op[0] == "conv" and r[2] is not None   # first layer of a phase-resident run
+            if opens:
+                x_ph, x = x, r[2]                            # the input gradient leaves in image layout
             last = i == 0
             if last and self.image_input:
                 tgt = None
@@ -147,7 +193,17 @@ class ChainPlan:
             acc = accumulate and last and gx is not None
             kind = op[0]
             if kind == "conv":
-                for p, gp in op[1].backward(tape, g, tgt, accumulate_gx=acc).items():
+                if r[3] is not None:  # last layer of a phase-resident run: g arrives in image layout
+                    gs = Act(torch.empty_like(r[1].buf))
+                    K.space_to_batch(g, r[3][0], gs)
+                    g = gs
+                if opens and tgt is not None:
+                    t_ph = Act(torch.empty_like(x_ph.buf))
+                    gr = op[1].backward(tape, g, t_ph)
+                    K.batch_to_space(t_ph, op[1].dil, tgt, accumulate=acc)
+                else:
+                    gr = op[1].backward(tape, g, tgt, accumulate_gx=acc)
+                for p, gp in gr.items():
                     E._acc(grads, p, gp)
             elif kind == "pool":
                 K.maxpool_bwd(x, g, tgt, accumulate=acc)

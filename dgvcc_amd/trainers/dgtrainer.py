@@ -51,6 +51,17 @@ class DGTrainer(Trainer):
         if name == "MSELoss":
             _, gt_dmaps, _ = gt_datas
             gt_dmaps = gt_dmaps.to(self.device, non_blocking=True)
+            if pred_dmaps.shape != gt_dmaps.shape:
+                # a reduced-resolution prediction (CSRNet: 1/8): the ground truth is sum-pooled onto
+                # the prediction's grid, which keeps its count
+                ph, pw = pred_dmaps.shape[-2:]
+                gh, gw = gt_dmaps.shape[-2:]
+                s = gh // ph if ph else 0
+                if (pred_dmaps.dim() != 4 or gt_dmaps.dim() != 4 or pred_dmaps.shape[:2] != gt_dmaps.shape[:2]
+                        or s < 2 or (ph * s, pw * s) != (gh, gw)):
+                    raise ValueError(f"MSELoss: prediction {tuple(pred_dmaps.shape)} is neither the ground truth's "
+                                     f"shape {tuple(gt_dmaps.shape)} nor smaller by one integer factor in H and W")
+                gt_dmaps = sum_pool(gt_dmaps, s)
             if weights is not None:
                 pred_dmaps = pred_dmaps * weights
                 gt_dmaps = gt_dmaps * weights

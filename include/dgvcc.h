@@ -543,6 +543,18 @@ int dg_upsample_fwd(int dtype, const void* x, int64_t ldx, int N, int H, int W, 
 int dg_upsample_bwd(int dtype, const void* gy, int64_t ldgy, const void* gy2, int64_t ldgy2,
                     int N, int H, int W, int C, int scale, int mode, void* gx, int64_t ldgx,
                     int accumulate, void* stream);
+/* Polyphase layout passes (a stride-1 3x3 convolution with dilation d, padding d is the dense pad-1
+ * convolution on the d*d phase sub-images).  With Hp = ceil(H/d), Wp = ceil(W/d):
+ * dg_space_to_batch: x [N,H,W,C] -> y [N*d*d,Hp,Wp,C], y[(n*d+i)*d+j][hp][wp] (+)= x[n][hp*d+i][wp*d+j],
+ * zero where the source lies outside the image; dg_batch_to_space: x [N*d*d,Hp,Wp,C] -> y [N,H,W,C], the
+ * inverse (positions outside H x W dropped).  N, H, W are the image-layout sizes in both.  Each is the
+ * other's adjoint.  Every destination element is written once; accumulate != 0 adds to it instead.
+ * C * sizeof(element) and both pixel strides in bytes must be multiples of 16 (else DG_ERR_UNSUPPORTED);
+ * d == 1 is a plain strided copy. */
+int dg_space_to_batch(int dtype, const void* x, int64_t ldx, int N, int H, int W, int C, int d,
+                      void* y, int64_t ldy, int accumulate, void* stream);
+int dg_batch_to_space(int dtype, const void* x, int64_t ldx, int N, int H, int W, int C, int d,
+                      void* y, int64_t ldy, int accumulate, void* stream);
 
 /* den_dec on the decomposed decoder concatenation (models/models.py:84,89-90):
  * conv1x1(cat[y1, up2(y2), up4(y3)]) = z1 + up2(z2) + up4(z3) with zk = conv1x1(yk; W[:, slice k]).
