@@ -304,6 +304,30 @@ __global__ __launch_bounds__(NT) void softmax_pair_bwd(const T* __restrict__ P1,
   }
 }
 
+// 2 log pm - log p1 - log p2 = log1p((p1 - p2)^2 / (4 p1 p2)) as a function of x = log p1 - log p2.
+// |x| <= 1: log1p(e^2 / (4 (1 + e))), e = expm1(x): no cancellation between the three O(log C) logs.  That
+// form leaves float range for well-separated views (expm1f(x) == -1 for x < -17.33: x / 0; e * e overflows for
+// x > 44.3), so beyond |x| = 1 the symmetric |x| + 2 log1p(exp(-|x|)) - 2 ln 2 is used: finite for every
+// finite x, its terms O(|x|) against a value >= 0.24.
+__device__ __forceinline__ float jsd_term(float x) {
+  const float ax = fabsf(x);
+  if (ax > 1.f) return ax + 2.f * log1pf(expf(-ax)) - 1.3862943611f;
+  const float e = expm1f(x);
+  return log1pf(e * e / (4.f * (1.f + e)));
+}
+
+// log of a stored probability in the KL-JSD backwards.  A stored zero (f16 rounds p < 3e-8 to 0) reads as
+// log(tiny_T), tiny_T half the smallest positive subnormal of the storage type (2^-25 f16, 2^-134 bf16,
+// 2^-150 f32): the largest value that rounds to zero, instead of log(0) = -inf, which made A = +inf and the
+// whole row's gradients non-finite when only one view's probability was stored as zero.
+template <typename T>
+__device__ __forceinline__ float log_stored(float p) {
+  constexpr float log_tiny = std::is_same<T, f16>::value ? -17.3286795f      // -25 ln 2
+                             : std::is_same<T, bf16>::value ? -92.8817222f   // -134 ln 2
+                                                            : -103.9720771f;  // -150 ln 2
+  return p > 0.f ? logf(p) : log_tiny;
+}
+
 // JSD of the two slot posteriors as models2.DensityRegressorM.forward_train computes it
 // (models/models2.py:339-346): pm = (p1 + p2)/2,
 //   loss_kl = 0.5/HW * (kl_div(log p1, pm, batchmean) + kl_div(log p2, pm, batchmean))
@@ -335,10 +359,8 @@ __global__ __launch_bounds__(NT) void softmax_jsd_fwd(const T* __restrict__ L1, 
     for (int j = 0; j < EPL; ++j) {
       a[j] *= ra; b[j] *= rb;
       const float pm = 0.5f * (a[j] + b[j]);
-      // 2 log pm - log p1 - log p2 = log1p((p1 - p2)^2 / (4 p1 p2)) = log1p(e^2 / (4 (1 + e))),
-      // e = expm1(log p1 - log p2): no cancellation between the three O(log C) logs
-      const float e = expm1f((la[j] - lb[j]) - dls);
-      if (pm > 0.f) acc += pm * log1pf(e * e / (4.f * (1.f + e)));
+      // 2 log pm - log p1 - log p2 from x = log p1 - log p2 (jsd_term)
+      if (pm > 0.f) acc += pm * jsd_term((la[j] - lb[j]) - dls);
     }
     store_row(P1 + r * C, lane, a, EPL);
     store_row(P2 + r * C, lane, b, EPL);
@@ -351,7 +373,8 @@ __global__ __launch_bounds__(NT) void softmax_jsd_fwd(const T* __restrict__ L1, 
 }
 
 // d loss_kl / d l1_j = k (p1_j (A_j - S1 + 1) - pm_j),  A = log pm - (log p1 + log p2)/2,
-// S1 = sum_j p1_j A_j, k = coef / (2 M); plus the readout's p1 (gP1 - <p1, gP1>).
+// S1 = sum_j p1_j A_j, k = coef / (2 M); plus the readout's p1 (gP1 - <p1, gP1>).  The logarithm of a
+// probability stored as zero in one view only is log_stored's log(tiny_T).
 template <typename T, int EPL>
 __global__ __launch_bounds__(NT) void softmax_jsd_bwd(const T* __restrict__ P1, const T* __restrict__ P2,
                                                       const T* __restrict__ G1, const T* __restrict__ G2, int M,
@@ -374,18 +397,19 @@ __global__ __launch_bounds__(NT) void softmax_jsd_bwd(const T* __restrict__ P1, 
       // A = log pm - (log p1 + log p2)/2 = log1p((p1-p2)^2 / (4 p1 p2)) / 2 (cancellation-free)
       const float d = p1[j] - p2[j];
       A[j] = (p1[j] > 0.f && p2[j] > 0.f) ? 0.5f * log1pf(d * d / (4.f * p1[j] * p2[j]))
-                                          : (pm > 0.f ? logf(pm) - 0.5f * (logf(p1[j]) + logf(p2[j])) : 0.f);
+             : pm > 0.f                   ? logf(pm) - 0.5f * (log_stored<T>(p1[j]) + log_stored<T>(p2[j]))
+                                          : 0.f;
       s1 = fmaf(p1[j], g1[j], s1);
       s2 = fmaf(p2[j], g2[j], s2);
-      t1 += p1[j] > 0.f ? p1[j] * A[j] : 0.f;
-      t2 += p2[j] > 0.f ? p2[j] * A[j] : 0.f;
+      t1 += p1[j] * A[j];  // A is finite (log_stored), so a stored zero contributes 0
+      t2 += p2[j] * A[j];
     }
     s1 = wave_sum(s1); s2 = wave_sum(s2); t1 = wave_sum(t1); t2 = wave_sum(t2);
 #pragma unroll
     for (int j = 0; j < EPL; ++j) {
       const float pm = 0.5f * (p1[j] + p2[j]);
-      const float a1 = p1[j] > 0.f ? p1[j] * (A[j] - t1 + 1.f) : 0.f;
-      const float a2 = p2[j] > 0.f ? p2[j] * (A[j] - t2 + 1.f) : 0.f;
+      const float a1 = p1[j] * (A[j] - t1 + 1.f);
+      const float a2 = p2[j] * (A[j] - t2 + 1.f);
       g1[j] = p1[j] * (g1[j] - s1) + k * (a1 - pm);
       g2[j] = p2[j] * (g2[j] - s2) + k * (a2 - pm);
     }
@@ -599,10 +623,9 @@ __global__ __launch_bounds__(NT) void softmax_head_fwd(const T* __restrict__ L1,
     for (int j = 0; j < EPL; ++j) {
       a[j] *= ra;
       if (NV == 2) b[j] *= rb;
-      if (LOSS == 2) {  // cancellation-free 2 log pm - log p1 - log p2 (as softmax_jsd_fwd)
+      if (LOSS == 2) {  // 2 log pm - log p1 - log p2 (as softmax_jsd_fwd)
         const float pm = 0.5f * (a[j] + b[j]);
-        const float e = expm1f((la[j] - lb[j]) - dls);
-        if (pm > 0.f) acc += pm * log1pf(e * e / (4.f * (1.f + e)));
+        if (pm > 0.f) acc += pm * jsd_term((la[j] - lb[j]) - dls);
       }
       a[j] = to_f(from_f<T>(a[j]));  // the loss and the head see the stored probabilities
       if (NV == 2) b[j] = to_f(from_f<T>(b[j]));
@@ -680,9 +703,10 @@ __global__ __launch_bounds__(NT) void softmax_head_bwd(const T* __restrict__ P1,
         const float pm = 0.5f * (p1[j] + p2[j]);
         const float d = p1[j] - p2[j];
         A[j] = (p1[j] > 0.f && p2[j] > 0.f) ? 0.5f * log1pf(d * d / (4.f * p1[j] * p2[j]))
-                                            : (pm > 0.f ? logf(pm) - 0.5f * (logf(p1[j]) + logf(p2[j])) : 0.f);
-        t1 += p1[j] > 0.f ? p1[j] * A[j] : 0.f;
-        t2 += p2[j] > 0.f ? p2[j] * A[j] : 0.f;
+               : pm > 0.f                   ? logf(pm) - 0.5f * (log_stored<T>(p1[j]) + log_stored<T>(p2[j]))
+                                            : 0.f;
+        t1 += p1[j] * A[j];
+        t2 += p2[j] * A[j];
       }
       s1 = fmaf(p1[j], g1[j], s1);
       if (NV == 2) s2 = fmaf(p2[j], g2[j], s2);
@@ -696,8 +720,8 @@ __global__ __launch_bounds__(NT) void softmax_head_bwd(const T* __restrict__ P1,
       if (NV == 2) g2[j] = p2[j] * (g2[j] - s2);
       if (LOSS == 2) {
         const float pm = 0.5f * (p1[j] + p2[j]);
-        const float a1 = p1[j] > 0.f ? p1[j] * (A[j] - t1 + 1.f) : 0.f;
-        const float a2 = p2[j] > 0.f ? p2[j] * (A[j] - t2 + 1.f) : 0.f;
+        const float a1 = p1[j] * (A[j] - t1 + 1.f);
+        const float a2 = p2[j] * (A[j] - t2 + 1.f);
         g1[j] += k * (a1 - pm);
         g2[j] += k * (a2 - pm);
       }
@@ -710,8 +734,8 @@ __global__ __launch_bounds__(NT) void softmax_head_bwd(const T* __restrict__ P1,
         cm1[j] = fmaxf(cm1[j], fabsf(g1[j]));
         if (NV == 2) cm2[j] = fmaxf(cm2[j], fabsf(g2[j]));
       } else {
-        mx1 = fmaxf(mx1, fabsf(g1[j]));
-        if (NV == 2) mx2 = fmaxf(mx2, fabsf(g2[j]));
+        mx1 = fmaxf(mx1, fabsf(round_to<T>(g1[j])));  // of the stored values: rounding to T may round up
+        if (NV == 2) mx2 = fmaxf(mx2, fabsf(round_to<T>(g2[j])));
       }
     }
   }

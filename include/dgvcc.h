@@ -627,7 +627,12 @@ int dg_mul_f32(const float* a, const float* b, int64_t n, float* out, void* stre
 /* models2.DensityRegressorM.forward_train (models/models2.py:326-346): the two slot
  * softmaxes plus loss_kl = 0.5/HW (KL(p1||pm) + KL(p2||pm)) batchmean, pm = (p1+p2)/2;
  * backward adds k (p_v (A - <p_v, A> + 1) - pm), A = log pm - (log p1 + log p2)/2,
- * k = coef[0] / (2M), to the readout's softmax backward. */
+ * k = coef[0] / (2M), to the readout's softmax backward.
+ * Range: the forward term 2 log pm - log p1 - log p2 is finite for every finite x = log p1 - log p2
+ * (well-separated views included).  dg_softmax_jsd_bwd works from the stored P: the logarithm of a stored
+ * zero is read as log(tiny_T), tiny_T half the smallest positive subnormal of the storage type (2^-25 f16,
+ * 2^-134 bf16, 2^-150 f32), so a probability that f16 rounded to 0 in one view only leaves the row's
+ * gradients finite. */
 int dg_softmax_jsd_fwd(int dtype, const void* L1, const void* L2, int M, int C, void* P1, void* P2,
                        float* loss_kl, void* workspace, void* stream);
 int dg_softmax_jsd_bwd(int dtype, const void* P1, const void* P2, const void* G1, const void* G2,
@@ -639,7 +644,8 @@ int dg_softmax_jsd_bwd(int dtype, const void* P1, const void* P2, const void* G1
  *   loss (0 none, 1 mean((P1-P2)^2) as dg_softmax_pair_fwd, 2 KL-JSD as dg_softmax_jsd_fwd; nviews 2).
  *   P_v may be NULL (no backward: eval).  workspace: dg_mem_head_workspace(M, C) bytes.
  * dg_softmax_head_bwd: gL_v = P_v (gP_v - <P_v, gP_v>), gP_v = gpre_v v + loss term, gpre_v =
- *   act'(yh_v) gyh_v (gyh_v NULL = 0); GL NULL = head gradients only.  Leaves per-block
+ *   act'(yh_v) gyh_v (gyh_v NULL = 0); GL NULL = head gradients only.  loss 2: a stored zero's logarithm
+ *   is read as log(tiny_T), as in dg_softmax_jsd_bwd.  Leaves per-block
  *   partials of u = sum_px gpre P and sum gpre in the workspace for
  * dg_mem_head_grads: dmem[k][S] = w u^T (the readout's mem gradient; NULL = skip), gw[k] = mem u,
  *   gb = sum gpre (NULL = skip); fixed-order (deterministic) reductions. */
@@ -654,7 +660,7 @@ int dg_softmax_head_bwd(int dtype, int nviews, int loss, const void* P1, const v
                         float* amax, void* stream);
 /* amax (may be NULL): f32, the logit gradients' operand maxima with channels, view v at
  * v * words (words = 1 + C rounded up to a multiple of 4; word 0 max |gL_v|, word 1 + s slot s's);
- * 16-bit, amax[v] = max |gL_v|. */
+ * 16-bit, amax[v] = max |gL_v| of the stored (rounded) values. */
 int dg_mem_head_grads(void* workspace, int M, int C, const float* mem, const float* w, int k,
                       float* dmem, float* gw, float* gb, void* stream);
 /* loss_err = F.l1_loss(IN(y1), IN(y2)) (models/models2.py:334) from the instance-norm
