@@ -439,6 +439,93 @@ class ConvLayer:
         return grads
 
 
+class SmallConvLayer:
+    """Conv2d(k in {1,3,5,7,9}, stride 1, same pad, 1 <= Cin, Cout <= 64) [+ ReLU], no BatchNorm: the
+    small-channel kernels.  Input and output are NHWC Acts whose channel counts are
+    rounded up to multiples of 8 (`K.cpad8`), with exact zeros in the padded channels; the layer keeps
+    that invariant on its output and on the input gradient it writes.  Same forward / backward /
+    params contract as ConvLayer."""
+
+    KS = (1, 3, 5, 7, 9)
+
+    @staticmethod
+    def unsupported(conv: nn.Conv2d) -> str | None:
+        """Why `conv` lies outside the small-channel family (None: it is inside)."""
+        k = conv.kernel_size[0]
+        pad = conv.padding if isinstance(conv.padding, tuple) else (conv.padding, conv.padding)
+        ok = (tuple(conv.kernel_size) == (k, k) and k in SmallConvLayer.KS and tuple(conv.stride) == (1, 1)
+              and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and pad == ((k - 1) // 2, (k - 1) // 2)
+              and getattr(conv, "padding_mode", "zeros") == "zeros"
+              and 1 <= conv.in_channels <= 64 and 1 <= conv.out_channels <= 64)
+        if ok:
+            return None
+        return ("a small-channel convolution is supported as kernel_size (k, k) with k in {1,3,5,7,9}, stride (1, 1), "
+                "padding ((k-1)/2, (k-1)/2), dilation (1, 1), groups 1, 1 <= in_channels <= 64 and 1 <= out_channels "
+                f"<= 64; got in_channels={conv.in_channels}, out_channels={conv.out_channels}, kernel_size="
+                f"{tuple(conv.kernel_size)}, stride={tuple(conv.stride)}, padding={conv.padding}, dilation="
+                f"{tuple(conv.dilation)}, groups={conv.groups}")
+
+    def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d | None = None, act: int = ACT_RELU, first: bool = False):
+        if bn is not None:
+            raise ValueError("SmallConvLayer: BatchNorm on a small-channel layer (in_channels="
+                             f"{conv.in_channels}, out_channels={conv.out_channels}) is out of scope")
+        why = self.unsupported(conv)
+        if why is not None:
+            raise ValueError("SmallConvLayer: " + why)
+        self.conv, self.bn, self.act, self.first = conv, None, act, first
+        self.scope = "head"
+        self.dil, self.resident, self.pair_out = 1, False, False
+        self.R = conv.kernel_size[0]
+        self.pad = (self.R - 1) // 2
+        self.Cin, self.Cout = conv.in_channels, conv.out_channels
+        self.Cp_in, self.Cp_out = K.cpad8(self.Cin), K.cpad8(self.Cout)  # the Acts' channel counts
+
+    def params(self):
+        return [self.conv.weight] + ([self.conv.bias] if self.conv.bias is not None else [])
+
+    def _pack(self, dt, flip: bool):
+        return frozen(self, ("small", dt, flip), (self.conv.weight,),
+                      lambda: K.smallconv_pack(self.conv.weight.detach(), dt, flip=flip))
+
+    def forward(self, x: Act, out: Act, training: bool, tape: dict | None, drop=None, pool=None):
+        if drop is not None or pool is not None:
+            raise ValueError("SmallConvLayer: no channel mask and no fused pooling on a small-channel layer")
+        if (out.N, out.H, out.W) != (x.N, x.H, x.W) or out.C != self.Cp_out or x.C != self.Cp_in:
+            raise ValueError(f"SmallConvLayer: input {(x.N, x.H, x.W, x.C)} / output {(out.N, out.H, out.W, out.C)} "
+                             f"!= [N, H, W, {self.Cp_in}] / [N, H, W, {self.Cp_out}] (Cin {self.Cin}, Cout {self.Cout} "
+                             "padded to multiples of 8)")
+        K.set_scope(self.scope)
+        dt = out.buf.dtype
+        bias = self.conv.bias.detach() if self.conv.bias is not None else None
+        K.smallconv_fwd(x, self._pack(dt, False), self.Cin, self.Cout, self.R, out, bias, relu=self.act == ACT_RELU)
+        if tape is not None:
+            tape[self] = (x, out)
+
+    def backward(self, tape: dict, g: Act, gx: Act | None, accumulate_gx: bool = False, g_pool=None, gx_bn=None) -> dict:
+        if accumulate_gx or g_pool is not None:
+            raise ValueError("SmallConvLayer: the input gradient is written, not accumulated, and there is no pooled output")
+        K.set_scope(self.scope)
+        x, y = tape.pop(self)
+        if (g.N, g.H, g.W, g.C) != (y.N, y.H, y.W, y.C):
+            raise ValueError(f"SmallConvLayer: gradient {(g.N, g.H, g.W, g.C)} != output {(y.N, y.H, y.W, y.C)}")
+        if gx is not None and (gx.N, gx.H, gx.W, gx.C) != (x.N, x.H, x.W, x.C):
+            raise ValueError(f"SmallConvLayer: input gradient {(gx.N, gx.H, gx.W, gx.C)} != input {(x.N, x.H, x.W, x.C)}")
+        dz = g
+        if self.act == ACT_RELU:
+            dz = Act(K.nhwc(y.N, y.H, y.W, y.C, y.buf.dtype, y.buf.device))
+            K.relu_bwd(g, y, dz)
+        dev = y.buf.device
+        dw = torch.empty(self.conv.weight.shape, dtype=torch.float32, device=dev)
+        db = torch.empty(self.Cout, dtype=torch.float32, device=dev) if self.conv.bias is not None else None
+        K.smallconv_wgrad(x, dz, self.Cin, self.Cout, self.R, dw, db)
+        if gx is not None:
+            K.smallconv_dgrad(dz, self._pack(y.buf.dtype, True), self.Cin, self.Cout, self.R, gx)
+        grads = {self.conv.weight: dw}
+        if db is not None:
+            grads[self.conv.bias] = db
+        return grads
+
+
 class CatParts:
     """The decoder concatenation y_cat = cat[y1, up2(y2), up4(y3)] (models/models.py:84) kept
     as its parts (NHWC Acts at their own resolutions) instead of a materialised

@@ -706,6 +706,73 @@ def batch_to_space(x: Act, d: int, y: Act, accumulate=False):
     y.pair = None
 
 
+# ---------------------------------------------------------------- small conv
+def cpad8(C: int) -> int:
+    """Channel count of a small-channel activation: C rounded up to a multiple of 8."""
+    return -(-C // 8) * 8
+
+
+def smallconv_pack(w: torch.Tensor, dtype: torch.dtype, flip: bool = False) -> torch.Tensor:
+    """Packed filter of w [Cout, C, R, S] for dg_smallconv_fwd; flip: the input gradient's filter."""
+    Cout, C, R, S = w.shape
+    n = query("dg_smallconv_pack_elems", dtype_code(dtype), Cout, C, R, S, int(flip))
+    wp = torch.empty(n, dtype=dtype, device=w.device)
+    call("dg_smallconv_pack", dtype_code(dtype), ptr(w.float().contiguous()), Cout, C, R, S, int(flip), ptr(wp),
+         stream())
+    return wp
+
+
+def _small_guard(a: Act, C: int, what: str):
+    if a.C != cpad8(C):
+        raise DGError(f"{what}: activation has {a.C} channels, expected {C} padded to {cpad8(C)}")
+
+
+def smallconv_fwd(x: Act, wp: torch.Tensor, C: int, Cout: int, R: int, y: Act, bias: torch.Tensor | None = None,
+                  relu: bool = False, stride: int = 1, pad: int | None = None, dil: int = 1, kind="fwd"):
+    """y = act(conv(x; wp) + bias): C -> Cout real channels, x / y padded to multiples of 8."""
+    _small_guard(x, C, "smallconv_fwd")
+    _small_guard(y, Cout, "smallconv_fwd")
+    _expect(y, x.N, x.H, x.W, cpad8(Cout), "smallconv_fwd")
+    pad = (R - 1) // 2 if pad is None else pad
+    flops = 2.0 * x.M * C * R * R * Cout
+    nbytes = x.buf.element_size() * (x.M * (x.C + y.C) + wp.numel())
+    _timed(kind, flops, lambda: call("dg_smallconv_fwd", x.dt, x.ptr, x.ld, x.N, x.H, x.W, C, ptr(wp), Cout, R, R,
+                                     stride, pad, dil, ptr(bias), int(relu), y.ptr, y.ld, stream()), nbytes)
+    y.amax = None
+    y.pair = None
+
+
+def smallconv_dgrad(dy: Act, wflip: torch.Tensor, C: int, Cout: int, R: int, dx: Act):
+    """dx = the input gradient of a C -> Cout layer: the forward on the flip-packed filter."""
+    smallconv_fwd(dy, wflip, Cout, C, R, dx, kind="dgrad")
+
+
+def smallconv_wgrad(x: Act, dy: Act, C: int, Cout: int, R: int, dw: torch.Tensor, dbias: torch.Tensor | None = None,
+                    stride: int = 1, pad: int | None = None, dil: int = 1):
+    """dw f32 [Cout, C, R, R] and dbias f32 [Cout] of a C -> Cout layer (deterministic slab sum)."""
+    _small_guard(x, C, "smallconv_wgrad")
+    _small_guard(dy, Cout, "smallconv_wgrad")
+    _expect(dy, x.N, x.H, x.W, cpad8(Cout), "smallconv_wgrad")
+    if dw.dtype != torch.float32 or tuple(dw.shape) != (Cout, C, R, R) or not dw.is_contiguous():
+        raise DGError(f"smallconv_wgrad: dw must be contiguous float32 {(Cout, C, R, R)}")
+    pad = (R - 1) // 2 if pad is None else pad
+    ws = query("dg_smallconv_wgrad_workspace", x.dt, x.N, x.H, x.W, C, Cout, R, R)
+    work = torch.empty(ws, dtype=torch.uint8, device=x.buf.device)
+    flops = 2.0 * x.M * C * R * R * Cout
+    nbytes = x.buf.element_size() * x.M * (x.C + dy.C) + 4.0 * dw.numel()
+    _timed("wgrad", flops, lambda: call("dg_smallconv_wgrad", x.dt, x.ptr, x.ld, dy.ptr, dy.ld, x.N, x.H, x.W, C, Cout,
+                                        R, R, stride, pad, dil, ptr(dw), ptr(dbias), ptr(work), ws, stream()), nbytes)
+
+
+def image_nhwc_pad(img: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """NCHW f32 image -> NHWC in dtype with the channels zero-padded to a multiple of 8."""
+    N, C, H, W = img.shape
+    y = nhwc(N, H, W, cpad8(C), dtype, img.device)
+    call("dg_image_nhwc_pad", dtype_code(dtype), ptr(img.float().contiguous()), N, C, H, W, ptr(y), y.shape[3],
+         y.shape[3], stream())
+    return y
+
+
 # ---------------------------------------------------------------- head -----
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 

@@ -27,13 +27,19 @@ class ChainPlan:
     output_layer).  A maximal run of consecutive convs with the same dilation d > 1 stays in phase
     layout (one dg_space_to_batch before it, one dg_batch_to_space after it) when the run's input has
     H % d == 0 and W % d == 0, decided per call; otherwise each dilated layer converts by itself
-    (DESIGN.md §3.3).  cat_input: the first op is the 1x1 conv on the decoder
+    (DESIGN.md §3.3).  A convolution the dense kernels take in no precision (out_channels % 64 != 0 or
+    in_channels % 32 != 0, the Cin=3 3x3 image stem apart) is an engine.SmallConvLayer:
+    its Acts carry channel counts rounded up to multiples of 8 with zero padded channels, which the
+    pools and the terminal head pass through.  cat_input: the first op is the 1x1 conv on the decoder
     concatenation parts (engine.CatConvLayer); image_input: the first conv reads the NCHW f32
-    image through the Cin=3 im2col (engine.ConvLayer first=True)."""
+    image through the Cin=3 im2col (engine.ConvLayer first=True), or, when it is a small-channel
+    layer, through dg_image_nhwc_pad; neither: an NHWC Act (such as the padded image several chains
+    share; input_grad=False then skips its gradient)."""
 
-    def __init__(self, modules, cat_input: bool = False, image_input: bool = False):
+    def __init__(self, modules, cat_input: bool = False, image_input: bool = False, input_grad: bool = True):
         mods = list(modules)
         self.cat_input, self.image_input = cat_input, image_input
+        self.input_grad = input_grad  # False: the Act input is a constant (a layout of the image)
         # runs of dilated convs stay in phase layout when H and W divide by d (decided per call);
         # False: every dilated layer converts in and out of image layout itself
         self.resident = True
@@ -82,13 +88,25 @@ class ChainPlan:
             if isinstance(m, (nn.Sigmoid, nn.Tanh)) and (not self.ops or self.ops[-1][0] != "head"):
                 raise ValueError("ChainPlan: Sigmoid/Tanh only after the terminal head")
 
+    @staticmethod
+    def is_small(conv, stem: bool) -> bool:
+        """The dense kernels take `conv` in no precision: it goes to the small-channel layer."""
+        if stem and conv.in_channels == 3 and tuple(conv.kernel_size) == (3, 3) and conv.out_channels % 64 == 0:
+            return False  # the image stem (im2col)
+        return conv.out_channels % 64 != 0 or conv.in_channels % 32 != 0
+
     def _conv(self, conv, bn, act, nxt):
         first = not self.ops
+        p = nxt.p if isinstance(nxt, nn.Dropout2d) else 0.0
         if first and self.cat_input:
             layer = E.CatConvLayer(conv, bn, act)
+        elif self.is_small(conv, first and self.image_input):
+            if p > 0:
+                raise ValueError(f"ChainPlan: Dropout2d after a small-channel convolution (in_channels="
+                                 f"{conv.in_channels}, out_channels={conv.out_channels}) is not supported")
+            layer = E.SmallConvLayer(conv, bn, act, first=first and self.image_input)
         else:
             layer = E.ConvLayer(conv, bn, act, first=first and self.image_input)
-        p = nxt.p if isinstance(nxt, nn.Dropout2d) else 0.0
         self.ops.append(["conv", layer, p])
         self._params += layer.params()
 
@@ -108,7 +126,8 @@ class ChainPlan:
         last conv op writes (a channel slice of a concatenation buffer), if given.
         Returns the last op's output: an Act, or the head's f32 [N,k,H,W] tensor."""
         if self.image_input:
-            x = Act(K.im2col_c3(x.float().contiguous(), dt))
+            small = self.ops and self.ops[0][0] == "conv" and isinstance(self.ops[0][1], E.SmallConvLayer)
+            x = Act(K.image_nhwc_pad(x, dt) if small else K.im2col_c3(x.float().contiguous(), dt))
         rec = []
         nops = len(self.ops)
         run_d, run_end, img = 1, -1, None  # inside a phase-resident run: its d, last op, image (N, H, W)
@@ -127,7 +146,7 @@ class ChainPlan:
                 dev = x.parts[0].buf.device if isinstance(x, E.CatParts) else x.buf.device
                 closes = run_d > 1 and i == run_end
                 y = out if (out is not None and i == nops - 1 and run_d == 1) \
-                    else Act(K.nhwc(N, H, W, layer.Cout, dt, dev))
+                    else Act(K.nhwc(N, H, W, getattr(layer, "Cp_out", layer.Cout), dt, dev))
                 n_img = img[0] if run_d > 1 else N  # Dropout2d draws one mask row per image
                 drop = E.dropout2d_mask(n_img, layer.Cout, p, dev) if (training and p > 0) else None
                 layer.resident = run_d > 1
@@ -152,7 +171,7 @@ class ChainPlan:
                 rec.append((x, y))
             else:  # head
                 conv, act, tanh = op[1], op[2], op[3]
-                w = conv.weight.detach()
+                w = _head_weight(conv, x.C)
                 ys = [K.head_fwd(x, w[k].reshape(-1).contiguous(),
                                  conv.bias.detach()[k:k + 1] if conv.bias is not None else None, act)
                       for k in range(conv.out_channels)]
@@ -182,7 +201,7 @@ class ChainPlan:
             if opens:
                 x_ph, x = x, r[2]                            # the input gradient leaves in image layout
             last = i == 0
-            if last and self.image_input:
+            if last and (self.image_input or not self.input_grad):
                 tgt = None
             elif last and gx is not None:
                 tgt = gx
@@ -217,14 +236,14 @@ class ChainPlan:
                     gpre = torch.empty_like(g)
                     K.call("dg_tanh_bwd", K.ptr(y), K.ptr(g), g.numel(), K.ptr(gpre), 0, K.stream())
                     g = gpre
-                w = conv.weight.detach()
+                w = _head_weight(conv, x.C)
                 gw = torch.empty((conv.out_channels, x.C), dtype=torch.float32, device=g.device)
                 gb = torch.empty(conv.out_channels, dtype=torch.float32, device=g.device) \
                     if conv.bias is not None else None
                 for k in range(conv.out_channels):
                     K.head_bwd(x, w[k].reshape(-1).contiguous(), act, ys[k], g[:, k].contiguous(), tgt, gw[k],
                                gb[k:k + 1] if gb is not None else None, accumulate_gx=(k > 0 or acc))
-                E._acc(grads, conv.weight, gw.view_as(conv.weight))
+                E._acc(grads, conv.weight, gw[:, :conv.in_channels].reshape(conv.weight.shape))
                 if gb is not None:
                     E._acc(grads, conv.bias, gb)
             g = tgt
@@ -250,6 +269,14 @@ class ChainPlan:
         if isinstance(gin, E.CatParts):
             return gin.tensors(), grads
         return (gin.buf,), grads
+
+
+def _head_weight(conv, C: int) -> torch.Tensor:
+    """The head's weight rows [k, C]: zero-extended when the Act carries padded channels."""
+    w = conv.weight.detach().reshape(conv.out_channels, -1)
+    if C < w.shape[1]:
+        raise ValueError(f"ChainPlan: head expects {w.shape[1]} channels, got {C}")
+    return w if C == w.shape[1] else torch.nn.functional.pad(w, (0, C - w.shape[1]))
 
 
 def run_chain(plan: ChainPlan, inputs, training: bool, dt: torch.dtype):

@@ -556,6 +556,34 @@ int dg_space_to_batch(int dtype, const void* x, int64_t ldx, int N, int H, int W
 int dg_batch_to_space(int dtype, const void* x, int64_t ldx, int N, int H, int W, int C, int d,
                       void* y, int64_t ldy, int accumulate, void* stream);
 
+/* Small-channel k x k convolution: R == S in {1,3,5,7,9}, stride 1, pad (R-1)/2,
+ * dilation 1, groups 1, 1 <= C <= 64, 1 <= Cout <= 64; anything else returns DG_ERR_UNSUPPORTED before
+ * any launch.  Activations are NHWC with the channel count rounded up to a multiple of 8 (Cp = 8*ceil(C/8),
+ * pixel stride ld >= Cp, 16-byte aligned) and exact zeros in the padded channels; every output written
+ * here has zeros in its padded channels whatever the buffer held.  16-bit types: v_mfma_f32_16x16x32;
+ * DG_F32: the exact v_mfma_f32_16x16x4_f32 in every dg_set_f32_math mode.
+ * dg_smallconv_pack: w f32 [Cout,C,R,S] -> the packed filter wp (dg_smallconv_pack_elems elements of
+ * dtype); flip != 0 packs the input gradient's filter (flipped taps, C and Cout exchanged).
+ * dg_smallconv_fwd: y[N,H,W,Cout_p] = act(conv(x[N,H,W,C_p]; wp) + bias), bias (f32 [Cout]) may be NULL,
+ * relu != 0 applies ReLU.  The input gradient of a layer (C -> Cout) is dg_smallconv_fwd with the
+ * flip-packed filter, C and Cout exchanged: dx = fwd(dy, wp_flip, C = Cout, Cout = C).
+ * dg_smallconv_wgrad: dw f32 [Cout,C,R,S] = sum over pixels of dy (x) x, dbias f32 [Cout] (may be NULL) =
+ * sum of dy; per-block partial sums go to `work` (dg_smallconv_wgrad_workspace bytes) and are added in
+ * block order: no atomics, bit-identical from run to run.
+ * dg_image_nhwc_pad: img f32 NCHW [N,C,H,W] -> y [N,H,W,Cp] in dtype, zeros in channels C .. Cp-1. */
+int64_t dg_smallconv_pack_elems(int dtype, int Cout, int C, int R, int S, int flip);
+int dg_smallconv_pack(int dtype, const float* w, int Cout, int C, int R, int S, int flip, void* wp,
+                      void* stream);
+int dg_smallconv_fwd(int dtype, const void* x, int64_t ldx, int N, int H, int W, int C, const void* wp,
+                     int Cout, int R, int S, int stride, int pad, int dil, const float* bias, int relu,
+                     void* y, int64_t ldy, void* stream);
+int64_t dg_smallconv_wgrad_workspace(int dtype, int N, int H, int W, int C, int Cout, int R, int S);
+int dg_smallconv_wgrad(int dtype, const void* x, int64_t ldx, const void* dy, int64_t lddy, int N, int H,
+                       int W, int C, int Cout, int R, int S, int stride, int pad, int dil, float* dw,
+                       float* dbias, void* work, int64_t work_bytes, void* stream);
+int dg_image_nhwc_pad(int dtype, const float* img, int N, int C, int H, int W, void* y, int64_t ldy, int Cp,
+                      void* stream);
+
 /* den_dec on the decomposed decoder concatenation (models/models.py:84,89-90):
  * conv1x1(cat[y1, up2(y2), up4(y3)]) = z1 + up2(z2) + up4(z3) with zk = conv1x1(yk; W[:, slice k]).
  * z [N,H,W,C] = z1 + up2(z2 [N,H/2,W/2,C]) + up4(z3 [N,H/4,W/4,C]) + bias (bilinear,
