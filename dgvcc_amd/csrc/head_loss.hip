@@ -587,6 +587,22 @@ __global__ void tanh_bwd_kernel(const float* __restrict__ y, const float* __rest
   }
 }
 
+__global__ void abs_fwd_kernel(const float* __restrict__ z, long long n, float* __restrict__ y) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    y[i] = fabsf(z[i]);
+}
+
+// gz = g sign(z), sign(+-0) = 0 (torch.abs's gradient); -g is exact, g * 0.f keeps g's sign on the zero
+__global__ void abs_bwd_kernel(const float* __restrict__ z, const float* __restrict__ gy, long long n,
+                               float* __restrict__ gz, int acc) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float v = z[i];
+    const float s = v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f);
+    const float g = gy[i] * s;
+    gz[i] = acc ? gz[i] + g : g;
+  }
+}
+
 }  // namespace
 
 extern "C" int dg_dmap_adaptive(const float* points, const int64_t* offsets, int N, int H, int W, double* sigma_ws,
@@ -732,6 +748,23 @@ extern "C" int dg_tanh_bwd(const float* y, const float* gy, int64_t n, float* gx
   DG_REQUIRE(y && gy && gx && n > 0);
   const int grid = (int)std::min<long long>(16384, (n + 255) / 256);
   hipLaunchKernelGGL(tanh_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, gy, (long long)n, gx,
+                     accumulate);
+  DG_CHECK_LAUNCH();
+  return DG_OK;
+}
+
+extern "C" int dg_abs_fwd(const float* z, int64_t n, float* y, void* stream) {
+  DG_REQUIRE(z && y && n > 0);
+  const int grid = (int)std::min<long long>(16384, (n + 255) / 256);
+  hipLaunchKernelGGL(abs_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, (long long)n, y);
+  DG_CHECK_LAUNCH();
+  return DG_OK;
+}
+
+extern "C" int dg_abs_bwd(const float* z, const float* gy, int64_t n, float* gz, int accumulate, void* stream) {
+  DG_REQUIRE(z && gy && gz && n > 0);
+  const int grid = (int)std::min<long long>(16384, (n + 255) / 256);
+  hipLaunchKernelGGL(abs_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, gy, (long long)n, gz,
                      accumulate);
   DG_CHECK_LAUNCH();
   return DG_OK;

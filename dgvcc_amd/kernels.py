@@ -793,6 +793,21 @@ def head_bwd(x: Act, w, act, y, gy, gx: Act | None, gw, gbias=None, accumulate_g
         gx.amax = None
 
 
+def abs_fwd(z: torch.Tensor) -> torch.Tensor:
+    """|z| of a contiguous f32 tensor (dg_abs_fwd)."""
+    y = torch.empty_like(z)
+    call("dg_abs_fwd", ptr(z), z.numel(), ptr(y), stream())
+    return y
+
+
+def abs_bwd(z: torch.Tensor, gy: torch.Tensor, gz: torch.Tensor | None = None, accumulate=False) -> torch.Tensor:
+    """gz (+)= gy sign(z), sign(+-0) = 0, from the signed pre-activation z (dg_abs_bwd)."""
+    if gz is None:
+        gz = torch.empty_like(z)
+    call("dg_abs_bwd", ptr(z), ptr(gy), z.numel(), ptr(gz), int(accumulate), stream())
+    return gz
+
+
 # ---------------------------------------------------------------- loss/opt -
 def mse_loss(pred: torch.Tensor, gt: torch.Tensor, gt_scale: float, want_grad=True, grad_coef=1.0):
     n = pred.numel()

@@ -113,11 +113,14 @@ def _bl_train_params(cfg):
     return dict(params, bl_targets=True)
 
 
-def load_config(config_path, task):
-    """(init_params, task_params) exactly as main.py:102-136."""
+def load_config(config_path, task, model_factory=None, simple=None):
+    """(init_params, task_params) exactly as main.py:102-136.  model_factory: the `get_model` to build
+    the model with (this module's when None); simple: run as DGTrainer 'simple' mode with the config's
+    `patch_size` or 10000, as main_base.py's BaseTrainer (None: for the names in _BASE_MODELS only)."""
     with open(config_path) as f:
         cfg = yaml.load(f, Loader=yaml.SafeLoader)
-    if cfg["model"]["name"] in _BASE_MODELS:
+    model_factory = model_factory or get_model
+    if simple if simple is not None else cfg["model"]["name"] in _BASE_MODELS:
         cfg = dict(cfg, mode="simple", patch_size=cfg.get("patch_size", 10000))
     init_params = {k: cfg[k] for k in ("seed", "version", "device", "log_para", "patch_size", "mode")}
     seed_everything(cfg["seed"])
@@ -125,7 +128,7 @@ def load_config(config_path, task):
     if D.world() > 1:  # one process per GPU under torchrun: this rank's device
         init_params["device"] = (f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available()
                                  else "cpu")
-    task_params = {"model": get_model(cfg["model"]["name"], cfg["model"]["params"]),
+    task_params = {"model": model_factory(cfg["model"]["name"], cfg["model"]["params"]),
                    "checkpoint": cfg["checkpoint"]}
     generator = get_seeded_generator(cfg["seed"])
     if task in ("train", "train_test"):
@@ -155,7 +158,7 @@ def load_config(config_path, task):
     return init_params, task_params
 
 
-def main(argv=None):
+def main(argv=None, loader=None):
     from .trainers.dgtrainer import DGTrainer
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="configs/dg.yaml", help="path to config file")
@@ -163,7 +166,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from . import dist as D
     D.init_from_env()  # torchrun: one process per GPU, RCCL; a no-op for a single process
-    init_params, task_params = load_config(args.config, args.task)
+    init_params, task_params = (loader or load_config)(args.config, args.task)
     trainer = DGTrainer(**init_params)
     if D.rank() == 0:
         shutil.copy(args.config, trainer.log_dir)

@@ -8,12 +8,17 @@
            5/3/3/3 filters, 3..48 channels, no BatchNorm, two MaxPool2d(2) each) on the same image,
            and a 1x1 30->1 layer on their concatenation; forward(x [B,3,H,W]) -> [B,1,H/4,W/4].
 
+  BL_VGG   models/baselines/BL.py:11-56: the sixteen VGG19 ("E") convolutions with four MaxPool2d(2)
+           (no BatchNorm), a x2 align-corners bilinear upsampling, 512->256->128 in 3x3, a 1x1 128->1
+           layer and torch.abs; forward(x [B,3,H,W]) -> [B,1,H/8,W/8], the Bayesian loss's grid.
+
 Same sub-module names, and therefore the same `state_dict` keys, as the reference
-(`tests/golden/csrnet_keys.json`, `tests/golden/mcnn_keys.json`).  CSRNet is one `plans2.ChainPlan`:
+(`tests/golden/csrnet_keys.json`, `tests/golden/mcnn_keys.json`, `tests/golden/blvgg_keys.json`).
+CSRNet is one `plans2.ChainPlan`:
 the dilated back end runs on the dense 3x3 kernels over the polyphase sub-images of its input
 (DESIGN.md §3.3).  MCNN's columns are three ChainPlans of small-channel layers on
 one padded NHWC image, writing into channel slices of one concatenation buffer that the 1x1 layer
-reads as a head.
+reads as a head.  BL_VGG is one ChainPlan whose head returns |z|.
 """
 from __future__ import annotations
 
@@ -24,9 +29,12 @@ from .. import engine as E
 from .. import kernels as K
 from ..kernels import Act
 from . import plans2 as P2
-from .models import _DGBase
+from .models import _DGBase, _load_pretrained_vgg
 
-__all__ = ["CSRNet", "MCNN", "make_layers"]
+__all__ = ["CSRNet", "MCNN", "VGG", "BL_VGG", "make_layers"]
+
+# reference models/baselines/BL.py:45-47
+cfg = {"E": [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512]}
 
 
 def make_layers(cfg, in_channels=3, batch_norm=False, dilation=False):
@@ -185,3 +193,46 @@ class MCNN(_DGBase):
         plan = self._plans["net"]
         dt, training = self.compute_dtype, self.training
         return E.run_plan(plan, lambda img, tape: plan.forward(img, dt, training, tape), (x,), plan.params())
+
+
+class VGG(_DGBase):
+    """reference models/baselines/BL.py:11-27: `features`, bilinear x2 (align_corners=True), `reg_layer`
+    and torch.abs, as one ChainPlan: the upsampling is dg_upsample_fwd's UP_BILINEAR_AC and the abs is
+    dg_abs_fwd on the head's map, with the signed map on the tape for dg_abs_bwd."""
+
+    def __init__(self, features):
+        super().__init__()
+        self._init_precision()
+        self.features = features
+        self.reg_layer = nn.Sequential(
+            nn.Conv2d(512, 256, kernel_size=3, padding=1),
+            nn.ReLU(inplace=True),
+            nn.Conv2d(256, 128, kernel_size=3, padding=1),
+            nn.ReLU(inplace=True),
+            nn.Conv2d(128, 1, 1))
+        self._plans = None
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_plans"] = None
+        return st
+
+    def forward(self, x):
+        if x.shape[-2] % 16 or x.shape[-1] % 16:
+            raise ValueError(f"BL_VGG: H, W must be multiples of 16 (got {x.shape[-2]}x{x.shape[-1]})")
+        if self._plans is None:
+            up = nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True)  # F.upsample_bilinear
+            mods = list(self.features) + [up] + list(self.reg_layer)
+            self._plans = {"net": P2.ChainPlan(mods, image_input=True, head_abs=True)}
+        return P2.run_chain(self._plans["net"], (x,), self.training, self.compute_dtype)
+
+
+def BL_VGG(pretrained=False):
+    """reference models/baselines/BL.py:49-56: VGG(make_layers(cfg["E"])).  The reference's
+    pretrained=True downloads torchvision's VGG19; this package never downloads: as the other models'
+    flag, it reads the file from the local torch hub cache if it is there and warns otherwise.  Load
+    weights with `load_state_dict`."""
+    model = VGG(make_layers(cfg["E"], batch_norm=False))
+    if pretrained:
+        _load_pretrained_vgg(model.features, "vgg19-dcbb9e9d.pth", "VGG19")
+    return model

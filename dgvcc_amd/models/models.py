@@ -38,13 +38,14 @@ def vgg16_bn_features() -> nn.Sequential:
     return nn.Sequential(*layers)
 
 
-def _load_pretrained_vgg(features: nn.Sequential) -> None:
+def _load_pretrained_vgg(features: nn.Sequential, filename: str = "vgg16_bn-6c64b313.pth",
+                         what: str = "VGG16-BN") -> None:
     """The reference downloads torchvision's VGG16_BN weights (models/models.py:35).
     There is no network here: use a local torchvision cache file if present."""
     home = os.environ.get("TORCH_HOME", os.path.expanduser("~/.cache/torch"))
-    path = os.path.join(home, "hub", "checkpoints", "vgg16_bn-6c64b313.pth")
+    path = os.path.join(home, "hub", "checkpoints", filename)
     if not os.path.exists(path):
-        warnings.warn("pretrained VGG16-BN weights unavailable offline; using random init")
+        warnings.warn(f"pretrained {what} weights unavailable offline; using random init")
         return
     sd = torch.load(path, map_location="cpu", weights_only=True)
     feats = {k[len("features."):]: v for k, v in sd.items() if k.startswith("features.")}

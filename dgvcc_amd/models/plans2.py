@@ -20,10 +20,14 @@ class ChainPlan:
     """A module sequence (nn.Sequential contents) run as NHWC HIP launches.
 
     Parsing: ConvBlock / (Conv2d [+ ReLU]) -> engine.ConvLayer, with a following Dropout2d
-    as its channel mask (F.dropout2d order: act, then mask); MaxPool2d(2) and bilinear
-    Upsample(x2); a final 1x1 ConvBlock with <= 4 output channels and no BN is the terminal
+    as its channel mask (F.dropout2d order: act, then mask); Conv2d + BatchNorm2d [+ ReLU] (what
+    baselines.make_layers(batch_norm=True) emits) is one ConvLayer too; MaxPool2d(2) and bilinear
+    Upsample by an integer factor (align_corners=True, nn.UpsamplingBilinear2d included, runs
+    UP_BILINEAR_AC); a final 1x1 ConvBlock with <= 4 output channels and no BN is the terminal
     head (one dg_head_fwd per output channel, ReLU / Sigmoid / none) and a trailing nn.Tanh
-    runs dg_tanh_fwd on it; a bare terminal nn.Conv2d(C, k <= 4, 1) is such a head too (CSRNet's
+    runs dg_tanh_fwd on it; head_abs=True returns |z| of an activation-free head (dg_abs_fwd; the tape
+    keeps z for dg_abs_bwd: BL's VGG19 counter); a bare terminal
+    nn.Conv2d(C, k <= 4, 1) is such a head too (CSRNet's
     output_layer).  A maximal run of consecutive convs with the same dilation d > 1 stays in phase
     layout (one dg_space_to_batch before it, one dg_batch_to_space after it) when the run's input has
     H % d == 0 and W % d == 0, decided per call; otherwise each dilated layer converts by itself
@@ -36,7 +40,8 @@ class ChainPlan:
     layer, through dg_image_nhwc_pad; neither: an NHWC Act (such as the padded image several chains
     share; input_grad=False then skips its gradient)."""
 
-    def __init__(self, modules, cat_input: bool = False, image_input: bool = False, input_grad: bool = True):
+    def __init__(self, modules, cat_input: bool = False, image_input: bool = False, input_grad: bool = True,
+                 head_abs: bool = False):
         mods = list(modules)
         self.cat_input, self.image_input = cat_input, image_input
         self.input_grad = input_grad  # False: the Act input is a constant (a layout of the image)
@@ -57,36 +62,49 @@ class ChainPlan:
                         if m.relu is not None:
                             raise ValueError("ChainPlan: ReLU followed by Sigmoid is not a supported head")
                         act = K.ACT_SIGMOID
-                    self.ops.append(["head", conv, act, isinstance(nxt, nn.Tanh)])
+                    self.ops.append(["head", conv, act, isinstance(nxt, nn.Tanh), False])
                     self._params += [conv.weight] + ([conv.bias] if conv.bias is not None else [])
                     continue
                 act = E.ACT_RELU if m.relu is not None else E.ACT_NONE
                 self._conv(conv, bn, act, nxt)
             elif isinstance(m, nn.Conv2d):
+                bn = nxt if isinstance(nxt, nn.BatchNorm2d) else None
                 if (not rest_has_conv and m.kernel_size == (1, 1) and m.out_channels <= 4 and self.ops
-                        and m.stride == (1, 1) and m.padding == (0, 0) and m.groups == 1):
+                        and m.stride == (1, 1) and m.padding == (0, 0) and m.groups == 1 and bn is None):
                     # a bare 1x1 terminal conv (CSRNet's output_layer) is a head as the ConvBlock one
                     act = K.ACT_RELU if isinstance(nxt, nn.ReLU) else K.ACT_NONE
                     if isinstance(nxt, nn.Sigmoid):
                         act = K.ACT_SIGMOID
-                    self.ops.append(["head", m, act, isinstance(nxt, nn.Tanh)])
+                    self.ops.append(["head", m, act, isinstance(nxt, nn.Tanh), False])
                     self._params += [m.weight] + ([m.bias] if m.bias is not None else [])
                     continue
-                self._conv(m, None, E.ACT_RELU if isinstance(nxt, nn.ReLU) else E.ACT_NONE, None)
+                if bn is not None:  # Conv2d, BatchNorm2d [, ReLU] (make_layers(batch_norm=True))
+                    nxt = mods[i + 2] if i + 2 < len(mods) else None
+                self._conv(m, bn, E.ACT_RELU if isinstance(nxt, nn.ReLU) else E.ACT_NONE, None)
+            elif isinstance(m, nn.BatchNorm2d) and i > 0 and isinstance(mods[i - 1], nn.Conv2d):
+                continue  # the BatchNorm of the ConvLayer before
             elif isinstance(m, nn.MaxPool2d):
                 if m.kernel_size not in (2, (2, 2)) or m.stride not in (2, (2, 2)):
                     raise ValueError("ChainPlan: only MaxPool2d(2, 2)")
                 self.ops.append(["pool"])
             elif isinstance(m, nn.Upsample):
-                if m.mode != "bilinear" or m.align_corners:
-                    raise ValueError("ChainPlan: only bilinear align_corners=False upsampling")
-                self.ops.append(["up", int(m.scale_factor)])
+                s = m.scale_factor
+                if m.mode != "bilinear" or not isinstance(s, (int, float)) or s != int(s) or s < 1:
+                    raise ValueError(f"ChainPlan: only bilinear upsampling by an integer scale_factor (got mode="
+                                     f"{m.mode!r}, scale_factor={s!r}, size={m.size!r})")
+                self.ops.append(["up", int(s), K.UP_BILINEAR_AC if m.align_corners else K.UP_BILINEAR])
             elif isinstance(m, (nn.ReLU, nn.Dropout2d, nn.Sigmoid, nn.Tanh)):
                 continue  # consumed by the op before (checked there)
             else:
                 raise ValueError(f"ChainPlan: unsupported module {type(m).__name__}")
             if isinstance(m, (nn.Sigmoid, nn.Tanh)) and (not self.ops or self.ops[-1][0] != "head"):
                 raise ValueError("ChainPlan: Sigmoid/Tanh only after the terminal head")
+        if head_abs:
+            head = self.ops[-1] if self.ops and self.ops[-1][0] == "head" else None
+            if head is None or head[2] != K.ACT_NONE or head[3]:
+                raise ValueError("ChainPlan: head_abs needs a terminal head without activation "
+                                 "(no ReLU / Sigmoid / Tanh)")
+            head[4] = True
 
     @staticmethod
     def is_small(conv, stem: bool) -> bool:
@@ -167,7 +185,7 @@ class ChainPlan:
             elif kind == "up":
                 s = op[1]
                 y = Act(K.nhwc(x.N, x.H * s, x.W * s, x.C, x.buf.dtype, x.buf.device))
-                K.upsample_fwd(x, s, K.UP_BILINEAR, y)
+                K.upsample_fwd(x, s, op[2], y)
                 rec.append((x, y))
             else:  # head
                 conv, act, tanh = op[1], op[2], op[3]
@@ -180,7 +198,10 @@ class ChainPlan:
                     t = torch.empty_like(y)
                     K.call("dg_tanh_fwd", K.ptr(y), y.numel(), K.ptr(t), K.stream())
                     y = t
-                rec.append((x, ys, y))
+                z = None
+                if op[4]:
+                    z, y = y, K.abs_fwd(y)  # the tape keeps the signed z: |z| has lost the sign
+                rec.append((x, ys, y, z))
             x = y
         if tape is not None:
             tape[self] = rec
@@ -227,11 +248,13 @@ class ChainPlan:
             elif kind == "pool":
                 K.maxpool_bwd(x, g, tgt, accumulate=acc)
             elif kind == "up":
-                K.upsample_bwd(g, op[1], K.UP_BILINEAR, tgt, accumulate=acc)
+                K.upsample_bwd(g, op[1], op[2], tgt, accumulate=acc)
             else:
                 conv, act, tanh = op[1], op[2], op[3]
                 ys, y = r[1], r[2]
                 g = g.float().contiguous()
+                if op[4]:
+                    g = K.abs_bwd(r[3], g)
                 if tanh:
                     gpre = torch.empty_like(g)
                     K.call("dg_tanh_bwd", K.ptr(y), K.ptr(g), g.numel(), K.ptr(gpre), 0, K.stream())

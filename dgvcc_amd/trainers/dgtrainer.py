@@ -72,6 +72,9 @@ class DGTrainer(Trainer):
                 # full-resolution map in log_para units is pooled onto the loss's grid in counts
                 gts, targs, st_sizes = gt_datas.bl
                 stride, G = int(loss.cfg["stride"]), loss.G
+                if tuple(pred_dmaps.shape[-2:]) == (G, G):
+                    # a counter that predicts on the loss's grid (BL_VGG: 1/8): only the units change
+                    return loss(gts, st_sizes, targs, sum_pool(pred_dmaps.float(), 1, 1.0 / self.log_para))
                 if pred_dmaps.shape[-2] != G * stride or pred_dmaps.shape[-1] != G * stride:
                     raise ValueError(f"BL expects a {G * stride}x{G * stride} prediction (grid {G} x stride "
                                      f"{stride}), got {pred_dmaps.shape[-2]}x{pred_dmaps.shape[-1]}")

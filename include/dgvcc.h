@@ -705,6 +705,10 @@ int dg_in_l1_bwd(int dtype, const void* y1, const void* y2, int64_t ld, int N, i
  * backward gx (+)= gy (1 - y^2) from the saved output. */
 int dg_tanh_fwd(const float* x, int64_t n, float* y, void* stream);
 int dg_tanh_bwd(const float* y, const float* gy, int64_t n, float* gx, int accumulate, void* stream);
+/* torch.abs on the BL VGG19 counter's output (models/baselines/BL.py:27): y = |z|; backward
+ * gz (+)= gy sign(z) with sign(+-0) = 0, from the signed pre-activation z (|z| has lost the sign). */
+int dg_abs_fwd(const float* z, int64_t n, float* y, void* stream);
+int dg_abs_bwd(const float* z, const float* gy, int64_t n, float* gz, int accumulate, void* stream);
 
 /* ---- losses ------------------------------------------------------------------
  * nn.MSELoss()(pred, gt*log_para) (trainers/dgtrainer.py:57): loss (f32 scalar
