@@ -286,7 +286,7 @@ __device__ __forceinline__ Tap src_tap(int o, int in, int out, int scale, int mo
     src = r * o;
   } else {
     const float r = 1.0f / (float)scale;
-    src = r * (o + 0.5f) - 0.5f;
+    src = r * (o + 0.5f) - 0.5f;  // contracted to one fma (one rounding), as in ATen's builds
     if (src < 0.f) src = 0.f;
   }
   int i0 = (int)src;
@@ -798,6 +798,7 @@ extern "C" int dg_upsample_bwd(int dtype, const void* gy, int64_t ldgy, const vo
 extern "C" int dg_maxpool_fwd(int dtype, const void* x, int64_t ldx, int N, int H, int W, int C, int k, int stride,
                               int pad, void* y, int64_t ldy, void* stream) {
   DG_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && 2 * pad <= k);
+  DG_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);  // C division would make P = 1 of a window that does not fit
   DG_REQUIRE(dtype == DG_F32 || DG_IS16(dtype));
   const int V = DG_IS16(dtype) ? 8 : 4;
   DG_SUPPORTED(C % V == 0 && ldx % V == 0 && ldy % V == 0);
@@ -820,6 +821,7 @@ extern "C" int dg_maxpool_fwd(int dtype, const void* x, int64_t ldx, int N, int 
 extern "C" int dg_maxpool_bwd(int dtype, const void* x, int64_t ldx, const void* gy, int64_t ldgy, int N, int H, int W,
                               int C, int k, int stride, int pad, void* gx, int64_t ldgx, int accumulate, void* stream) {
   DG_REQUIRE(x && gy && gx && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && 2 * pad <= k);
+  DG_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);  // C division would make P = 1 of a window that does not fit
   DG_REQUIRE(dtype == DG_F32 || DG_IS16(dtype));
   const int V = DG_IS16(dtype) ? 8 : 4;
   DG_SUPPORTED(C % V == 0 && ldx % V == 0 && ldgy % V == 0 && ldgx % V == 0);
@@ -843,6 +845,7 @@ extern "C" int dg_maxpool_fwd_idx(int dtype, const void* x, int64_t ldx, int N, 
                                   int pad, void* y, int64_t ldy, unsigned char* idx, void* stream) {
   DG_REQUIRE(x && y && idx && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && k <= 15 && stride > 0 && pad >= 0 &&
              2 * pad <= k);
+  DG_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);  // C division would make P = 1 of a window that does not fit
   DG_REQUIRE(dtype == DG_F32 || DG_IS16(dtype));
   const int V = DG_IS16(dtype) ? 8 : 4;
   DG_SUPPORTED(C % V == 0 && ldx % V == 0 && ldy % V == 0 && (long long)N * H * W * (C / V) < (1LL << 30));
@@ -867,6 +870,7 @@ extern "C" int dg_maxpool_bwd_idx(int dtype, const unsigned char* idx, const voi
                                   void* stream) {
   DG_REQUIRE(idx && gy && gx && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && k <= 15 && stride > 0 && pad >= 0 &&
              2 * pad <= k);
+  DG_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);  // C division would make P = 1 of a window that does not fit
   DG_REQUIRE(dtype == DG_F32 || DG_IS16(dtype));
   const int V = DG_IS16(dtype) ? 8 : 4;
   DG_SUPPORTED(C % V == 0 && ldgy % V == 0 && ldgx % V == 0 && (long long)N * H * W * (C / V) < (1LL << 30));

@@ -958,13 +958,32 @@ def unpack_c3(dwcol: torch.Tensor, dw: torch.Tensor, accumulate=False):
     call("dg_unpack_c3", ptr(dwcol), Cout, R, S, dwcol.shape[1], ptr(dw), int(accumulate), stream())
 
 
+def _pool_out(x: Act, k: int, stride: int, pad: int, what: str) -> tuple[int, int]:
+    """(P, Q) of the general pool; the window must fit the padded map (floor division gives 0 where C gives 1)."""
+    if k <= 0 or stride <= 0 or pad < 0 or 2 * pad > k or x.H + 2 * pad < k or x.W + 2 * pad < k:
+        raise DGError(f"{what}: no {k}x{k} window, stride {stride}, pad {pad}, on a {x.H}x{x.W} map")
+    return (x.H + 2 * pad - k) // stride + 1, (x.W + 2 * pad - k) // stride + 1
+
+
+def _expect_idx(idx: torch.Tensor, gy: Act, what: str):
+    if (tuple(idx.shape) != (gy.N, gy.H, gy.W, gy.C) or idx.dtype != torch.uint8 or idx.device != gy.buf.device
+            or not idx.is_contiguous()):
+        raise DGError(f"{what}: idx {tuple(idx.shape)} {idx.dtype} on {idx.device} != expected dense uint8 "
+                      f"{(gy.N, gy.H, gy.W, gy.C)} on {gy.buf.device}")
+
+
 def maxpool_k_fwd(x: Act, k: int, stride: int, pad: int, y: Act):
+    P, Q = _pool_out(x, k, stride, pad, "maxpool_k_fwd")
+    _expect(y, x.N, P, Q, x.C, "maxpool_k_fwd")
     call("dg_maxpool_fwd", x.dt, x.ptr, x.ld, x.N, x.H, x.W, x.C, k, stride, pad, y.ptr, y.ld,
          stream())
     y.amax = x.amax  # a window maximum never exceeds its channel's max |x|
 
 
 def maxpool_k_bwd(x: Act, gy: Act, k: int, stride: int, pad: int, gx: Act, accumulate=False):
+    P, Q = _pool_out(x, k, stride, pad, "maxpool_k_bwd")
+    _expect(gy, x.N, P, Q, x.C, "maxpool_k_bwd")
+    _expect(gx, x.N, x.H, x.W, x.C, "maxpool_k_bwd")
     call("dg_maxpool_bwd", x.dt, x.ptr, x.ld, gy.ptr, gy.ld, x.N, x.H, x.W, x.C, k, stride, pad,
          gx.ptr, gx.ld, int(accumulate), stream())
     gx.amax = None
@@ -972,6 +991,8 @@ def maxpool_k_bwd(x: Act, gy: Act, k: int, stride: int, pad: int, gx: Act, accum
 
 def maxpool_k_fwd_idx(x: Act, k: int, stride: int, pad: int, y: Act) -> torch.Tensor:
     """maxpool_k_fwd that also records each window's argmax (uint8 [N,P,Q,C]) for maxpool_k_bwd_idx."""
+    P, Q = _pool_out(x, k, stride, pad, "maxpool_k_fwd_idx")
+    _expect(y, x.N, P, Q, x.C, "maxpool_k_fwd_idx")
     idx = torch.empty((y.N, y.H, y.W, x.C), dtype=torch.uint8, device=x.buf.device)
     call("dg_maxpool_fwd_idx", x.dt, x.ptr, x.ld, x.N, x.H, x.W, x.C, k, stride, pad, y.ptr, y.ld,
          ptr(idx), stream())
@@ -980,6 +1001,9 @@ def maxpool_k_fwd_idx(x: Act, k: int, stride: int, pad: int, y: Act) -> torch.Te
 
 
 def maxpool_k_bwd_idx(idx: torch.Tensor, gy: Act, k: int, stride: int, pad: int, gx: Act, accumulate=False):
+    P, Q = _pool_out(gx, k, stride, pad, "maxpool_k_bwd_idx")
+    _expect(gy, gx.N, P, Q, gx.C, "maxpool_k_bwd_idx")
+    _expect_idx(idx, gy, "maxpool_k_bwd_idx")
     call("dg_maxpool_bwd_idx", gx.dt, ptr(idx), gy.ptr, gy.ld, gx.N, gx.H, gx.W, gx.C, k, stride, pad,
          gx.ptr, gx.ld, int(accumulate), stream())
     gx.amax = None
