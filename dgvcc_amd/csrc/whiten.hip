@@ -6,8 +6,8 @@
 //   instance); here live the masked-L1 loss + its gradient and the
 //   variance-of-covariance statistic of cal_covstat.
 //
-// SW (models/SW/ops/switchwhiten.py:84-183), sw_type 2 (BW + IW), groups of 16
-// channels: statistics with f32 MFMA (16x16x4: one group's 16x16 covariance per
+// SW (models/SW/ops/switchwhiten.py:84-183), sw_type 2 (BW + IW), 3 (+ LN) and 5 (+ BN + IN + LN),
+// groups of 16 channels: statistics with f32 MFMA (16x16x4: one group's 16x16 covariance per
 // wave), Newton-Schulz whitening matrices in one 256-thread block per group
 // (thread = matrix element), and a fused whiten+affine+ReLU apply.  Backward is
 // the exact adjoint (Newton iterations recomputed in LDS, no autograd tape).
@@ -206,6 +206,48 @@ __device__ __forceinline__ void softmax2(const float* w, float& a0, float& a1) {
   a1 = e1 / (e0 + e1);
 }
 
+// The mixing weights of one side (mean or covariance) folded onto the three statistic families
+// the kernels hold: bn (batch), in (instance), ln (layer).  sw_type 2: (w0, w1, -); 3: (w0, w1, w2);
+// 5: the mean takes (w0 + w2, w1 + w3, w4), the covariance (w0, w1, w4) -- its BN / IN variances
+// reuse w0 / w1 (switchwhiten.py:159-164), w2 and w3 enter through the normalisation alone.
+template <int SWT>
+__device__ __forceinline__ void sw_softmax(const float* w, float* a) {
+  if constexpr (SWT == 2) {
+    softmax2(w, a[0], a[1]);
+  } else {
+    float m = w[0];
+#pragma unroll
+    for (int k = 1; k < SWT; ++k) m = fmaxf(m, w[k]);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < SWT; ++k) {
+      a[k] = expf(w[k] - m);
+      s += a[k];
+    }
+#pragma unroll
+    for (int k = 0; k < SWT; ++k) a[k] /= s;
+  }
+}
+struct SwMix {
+  float bn, in, ln;
+};
+template <int SWT>
+__device__ __forceinline__ void sw_mix(const float* mean_w, const float* var_w, SwMix& a, SwMix& b) {
+  float wa[SWT], wb[SWT];
+  sw_softmax<SWT>(mean_w, wa);
+  sw_softmax<SWT>(var_w ? var_w : mean_w, wb);  // var_w NULL: tie_weight
+  a = SwMix{wa[0], wa[1], 0.f};
+  b = SwMix{wb[0], wb[1], 0.f};
+  if constexpr (SWT == 3) {
+    a.ln = wa[2];
+    b.ln = wb[2];
+  }
+  if constexpr (SWT == 5) {
+    a = SwMix{wa[0] + wa[2], wa[1] + wa[3], wa[4]};
+    b.ln = wb[4];
+  }
+}
+
 // Newton-Schulz whitening matrix of S (LDS, 256): P_{k+1} = 1.5 P_k - 0.5 P_k^3 (S/tr S),
 // W = P_T sqrt(1/tr S).  Ps[k] (k = 0..T) kept in LDS when Ps != nullptr.
 struct SwLds {
@@ -247,7 +289,7 @@ __device__ float sw_newton(SwLds& L, float* Ps, int T, int t) {
 }
 
 // Save layout (floats): mu_in[N][C] | cov_in[N][G][256] | mu_bn[C] | cov_bn[G][256]
-//                       | aff[N][G][256] | bias[N][C]
+//                       | aff[N][G][256] | bias[N][C] | ln[N][2] (mean_ln, var_ln; sw_type 3 and 5)
 // Batch moments (doubles, per group): S1[16] = sum_n mu_n, S2[256] = sum_n (cov_n + mu_n mu_n^T).
 // They are the only cross-instance quantities of BW, so SyncSwitchWhiten reduces exactly
 // these [G][272] doubles over ranks between sw_inst_stats and sw_finalize.
@@ -273,6 +315,46 @@ __global__ __launch_bounds__(256) void sw_inst_stats(const float* __restrict__ p
   cov_in[((long long)n * G + g) * 256 + t] = (float)(s / HW);
 }
 
+inline __host__ __device__ long long sw_save_floats(long long N, long long C) {
+  return 2 * N * C + 2 * N * (C / SWC) * 256 + C + (C / SWC) * 256;
+}
+
+__device__ __forceinline__ double block_sum256d(double v, double* red) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  red[t] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) red[t] += red[t + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// One block per instance (sw_type 3, 5): the layer statistics of x[n] over all C HW elements from
+// the instance statistics of every group, mean_ln = sum_c mu_c / C and the unbiased variance in the
+// centred form var_ln = HW sum_c (cov_cc + (mu_c - mean_ln)^2) / (C HW - 1)  (E[x^2] - mean^2
+// cancels in f32).  C <= 256: thread = channel.
+__global__ __launch_bounds__(256) void sw_ln_stats(int N, int HW, int C, float* __restrict__ save) {
+  __shared__ double red[256];
+  const int n = blockIdx.x, t = threadIdx.x, G = C / SWC;
+  const float* mu_in = save;
+  const float* cov_in = save + (long long)N * C;
+  float* ln = save + sw_save_floats(N, C);
+  const double mu = t < C ? (double)mu_in[(long long)n * C + t] : 0.0;
+  const double mean = block_sum256d(mu, red) / C;
+  double v = 0.0;
+  if (t < C) {
+    const double d = mu - mean;
+    v = (double)cov_in[((long long)n * G + (t >> 4)) * 256 + (t & 15) * 17] + d * d;
+  }
+  const double var = block_sum256d(v, red) * (double)HW / ((double)C * HW - 1.0);
+  if (t == 0) {
+    ln[2 * n] = (float)mean;
+    ln[2 * n + 1] = (float)var;
+  }
+}
+
 // One block per group: the batch moments over this rank's instances, in instance order.
 __global__ __launch_bounds__(256) void sw_moments(int N, int C, const float* __restrict__ save,
                                                   double* __restrict__ moments) {
@@ -293,7 +375,9 @@ __global__ __launch_bounds__(256) void sw_moments(int N, int C, const float* __r
 // One block per (group, instance): batch mean/cov from the (possibly all-reduced) moments
 // over `count` instances (or the running statistics in eval; recomputed per block, the
 // instance-0 block writes them and updates the running statistics), then this instance's
-// Newton-Schulz whitening matrix folded with the affine.
+// Newton-Schulz whitening matrix folded with the affine.  sw_type 3 and 5 add the diagonal
+// components (LN's var_ln I; for 5 also diag(cov_bn), diag(cov_in)) and mean_ln to the mixture.
+template <int SWT>
 __global__ __launch_bounds__(256) void sw_finalize(const double* __restrict__ moments, double count, int N, int C,
                                                    int T, float eps, float momentum, const float* mean_w,
                                                    const float* var_w, const float* gamma, const float* beta,
@@ -338,12 +422,20 @@ __global__ __launch_bounds__(256) void sw_finalize(const double* __restrict__ mo
     if (lead) cov_bn[g * 256 + t] = cbn;
   }
   __syncthreads();
-  float a0, a1, b0, b1;
-  softmax2(mean_w, a0, a1);
-  softmax2(var_w, b0, b1);
+  SwMix a, b;
+  sw_mix<SWT>(mean_w, var_w, a, b);
   const float ci = cov_in[((long long)n * G + g) * 256 + t];
-  L.S[t] = b0 * cbn + b1 * ci + (i == j ? eps : 0.f);
-  if (t < 16) L.vec[1][t] = a0 * L.vec[0][t] + a1 * mu_in[(long long)n * C + g * 16 + t];  // mixed mean
+  if constexpr (SWT == 2) {  // the statements of the BW + IW operator as they always were: same roundings
+    const float a0 = a.bn, a1 = a.in, b0 = b.bn, b1 = b.in;
+    L.S[t] = b0 * cbn + b1 * ci + (i == j ? eps : 0.f);
+    if (t < 16) L.vec[1][t] = a0 * L.vec[0][t] + a1 * mu_in[(long long)n * C + g * 16 + t];  // mixed mean
+  } else {
+    const float* ln = bias + (long long)N * C + 2 * n;
+    float sv = b.bn * cbn + b.in * ci + (i == j ? eps : 0.f);
+    if (i == j) sv += (SWT == 5 ? b.bn * cbn + b.in * ci : 0.f) + b.ln * ln[1];
+    L.S[t] = sv;
+    if (t < 16) L.vec[1][t] = a.bn * L.vec[0][t] + a.in * mu_in[(long long)n * C + g * 16 + t] + a.ln * ln[0];
+  }
   __syncthreads();
   const float r = sw_newton(L, nullptr, T, t);
   const float w = L.P[t] * sqrtf(r);
@@ -475,8 +567,12 @@ __global__ __launch_bounds__(256) void sw_bwd_partial(const T* __restrict__ gy, 
 //   dx_p = K ge_p + L (x_p - mu_n) + c.
 // The cross-instance sums leave as per-(n, g) rows of npart [n][g][SW_NP]:
 //   dcov_bn(256) | dmu_bn(16) | dgamma(16) | dbeta(16) | da0-da1 db0-db1
-// and sw_bwd_reduce adds them in instance order.
+// and sw_bwd_reduce adds them in instance order.  sw_type 3 and 5 append
+//   [306] da_ln-da_in  [307] db_ln-db_in  [308] -db_in  [309] dvar_ln part  [310] dmean_ln part
+// (adjoints of the softmax outputs relative to the instance component, which the softmax backward
+// is invariant to; the LN adjoints are summed over the instance's groups by sw_bwd_coef).
 constexpr int SW_NP = 320;
+template <int SWT>
 __global__ __launch_bounds__(256) void sw_bwd_small(const float* __restrict__ part, int N, int nb, int HW, int C, int T,
                                                     float eps, const float* mean_w, const float* var_w,
                                                     const float* gamma, const float* __restrict__ save,
@@ -489,9 +585,15 @@ __global__ __launch_bounds__(256) void sw_bwd_small(const float* __restrict__ pa
   const float* cov_in = mu_in + (long long)N * C;
   const float* mu_bn = cov_in + (long long)N * G * 256;
   const float* cov_bn = mu_bn + C;
-  float a0, a1, b0, b1;
-  softmax2(mean_w, a0, a1);
-  softmax2(var_w, b0, b1);
+  SwMix a, b;
+  sw_mix<SWT>(mean_w, var_w, a, b);
+  const float a0 = a.bn, a1 = a.in, b0 = b.bn, b1 = b.in;
+  float mean_ln = 0.f, var_ln = 0.f;
+  if constexpr (SWT != 2) {
+    const float* ln = save + sw_save_floats(N, C) + 2 * n;
+    mean_ln = ln[0];
+    var_ln = ln[1];
+  }
   const float cbn = cov_bn[g * 256 + t];
   const float gam_i = gamma ? gamma[g * 16 + i] : 1.f;
   const float gam_j = gamma ? gamma[g * 16 + j] : 1.f;
@@ -524,10 +626,18 @@ __global__ __launch_bounds__(256) void sw_bwd_small(const float* __restrict__ pa
   if (t < 16) {
     mv[0][t] = mu_bn[g * 16 + t];
     mv[2][t] = mu_in[(long long)n * C + g * 16 + t];
-    mv[1][t] = a0 * mv[0][t] + a1 * mv[2][t];
+    float mix = a0 * mv[0][t] + a1 * mv[2][t];
+    if constexpr (SWT != 2) mix += a.ln * mean_ln;
+    mv[1][t] = mix;
     mv[3][t] = sg;
   }
-  L.S[t] = b0 * cbn + b1 * ci + (i == j ? eps : 0.f);
+  {
+    float sv = b0 * cbn + b1 * ci + (i == j ? eps : 0.f);
+    if constexpr (SWT != 2) {
+      if (i == j) sv += (SWT == 5 ? b0 * cbn + b1 * ci : 0.f) + b.ln * var_ln;
+    }
+    L.S[t] = sv;
+  }
   __syncthreads();
   const float r = sw_newton(L, Ps, T, t);
   const float sr = sqrtf(r);
@@ -589,12 +699,33 @@ __global__ __launch_bounds__(256) void sw_bwd_small(const float* __restrict__ pa
   // mixing-weight adjoints in difference form: softmax2's backward only needs da0 - da1
   // (dtheta = a0 a1 (da0 - da1) (1, -1)), and summing dm (mu_bn - mu_n), dS (C_bn - C_n)
   // directly avoids the cancellation of two large sums
-  const float ddb = block_sum256(dS * (cbn - ci), L.red);
-  np[t] = b0 * dS;  // this instance's dcov_bn
+  // sw_type 5: the diagonal of cov_bn / cov_in enters S twice (cov + var), so does its adjoint
+  const float dSw = (SWT == 5 && i == j) ? 2.f * dS : dS;
+  const float ddb = block_sum256((SWT == 5 ? dSw : dS) * (cbn - ci), L.red);
+  np[t] = b0 * (SWT == 5 ? dSw : dS);  // this instance's dcov_bn
   // D_n = b1 (dS + dS^T) / HW  (stored in the L slot; E added by sw_bwd_coef)
   L.X[t] = dS;
   __syncthreads();
-  cf[256 + t] = b1 * (dS + L.X[j * 16 + i]) / (float)HW;
+  if constexpr (SWT == 5)
+    cf[256 + t] = b1 * (dSw + (i == j ? dSw : L.X[j * 16 + i])) / (float)HW;
+  else
+    cf[256 + t] = b1 * (dS + L.X[j * 16 + i]) / (float)HW;
+  if constexpr (SWT != 2) {
+    // LN: dvar_ln = b_ln tr(dS), dmean_ln = a_ln sum(dm) (this group's parts); mixing-weight
+    // adjoints of the LN (and, for 5, the weightless BN / IN) components against the instance one
+    const float trs = block_sum256(i == j ? dS : 0.f, L.red);
+    const float fl = block_sum256(dS * ((i == j ? var_ln : 0.f) - ci) - (SWT == 5 && i == j ? dS * ci : 0.f), L.red);
+    const float fz = SWT == 5 ? block_sum256(-dSw * ci, L.red) : 0.f;
+    const float el = block_sum256(t < 16 ? dm * (mean_ln - mv[2][t]) : 0.f, L.red);
+    const float sdm = block_sum256(t < 16 ? dm : 0.f, L.red);
+    if (t == 0) {
+      np[306] = el;
+      np[307] = fl;
+      np[308] = fz;
+      np[309] = b.ln * trs;
+      np[310] = a.ln * sdm;
+    }
+  }
   if (t < 16) {
     np[256 + t] = a0 * dm;               // dmu_bn
     cf[512 + t] = a1 * dm / (float)HW;  // dmu_n / HW (completed by sw_bwd_coef)
@@ -637,8 +768,12 @@ __global__ __launch_bounds__(256) void sw_bwd_reduce(const float* __restrict__ n
 
 // Completes coef with the batch terms: Esym = (dC + dC^T)/(count HW) added to L,
 // c += Esym (mu_n - mu_bn) + dmu_bn/(count HW); count = images over all ranks.
+// sw_type 3 and 5: LN's adjoints, summed here over the instance's groups (in group order, the same
+// sum in every block), add s I to L and s (mu_nc - mean_ln) + dmean_ln/(C HW) to c, s = 2 dvar_ln/(C HW - 1).
+template <int SWT>
 __global__ __launch_bounds__(256) void sw_bwd_coef(const double* __restrict__ bmoments, double count, int N, int HW,
-                                                   int C, const float* __restrict__ save, float* __restrict__ coef) {
+                                                   int C, const float* __restrict__ save,
+                                                   const float* __restrict__ npart, float* __restrict__ coef) {
   __shared__ float E[256];
   __shared__ float mb[16], dmu[16];
   const int g = blockIdx.x, G = C / SWC, t = threadIdx.x, i = t >> 4, j = t & 15;
@@ -652,13 +787,39 @@ __global__ __launch_bounds__(256) void sw_bwd_coef(const double* __restrict__ bm
     dmu[t] = (float)(bm[t] / den);
   }
   __syncthreads();
-  for (int n = 0; n < N; ++n) {
-    float* cf = coef + ((long long)n * G + g) * 528;
-    cf[256 + t] += E[t];
-    if (t < 16) {
-      float sacc = 0.f;
-      for (int k = 0; k < 16; ++k) sacc = fmaf(E[t * 16 + k], mu_in[(long long)n * C + g * 16 + k] - mb[k], sacc);
-      cf[512 + t] += sacc + dmu[t];
+  // LN adjoints of up to 256 instances at a time: thread = instance, groups added in order
+  __shared__ float sls[256], cls[256];
+  for (int n0 = 0; n0 < N; n0 += 256) {
+    if constexpr (SWT != 2) {
+      __syncthreads();
+      if (n0 + t < N) {
+        double dv = 0.0, dml = 0.0;
+        for (int q = 0; q < G; ++q) {
+          dv += npart[((long long)(n0 + t) * G + q) * SW_NP + 309];
+          dml += npart[((long long)(n0 + t) * G + q) * SW_NP + 310];
+        }
+        const double M = (double)C * HW;
+        sls[t] = (float)(2.0 * dv / (M - 1.0));
+        cls[t] = (float)(dml / M);
+      }
+      __syncthreads();
+    }
+    for (int n = n0; n < min(N, n0 + 256); ++n) {
+      float* cf = coef + ((long long)n * G + g) * 528;
+      if constexpr (SWT != 2)
+        cf[256 + t] += E[t] + (i == j ? sls[n - n0] : 0.f);
+      else
+        cf[256 + t] += E[t];
+      if (t < 16) {
+        float sacc = 0.f;
+        for (int k = 0; k < 16; ++k) sacc = fmaf(E[t * 16 + k], mu_in[(long long)n * C + g * 16 + k] - mb[k], sacc);
+        float add = sacc + dmu[t];
+        if constexpr (SWT != 2) {
+          const float mean_ln = save[sw_save_floats(N, C) + 2 * n];
+          add += sls[n - n0] * (mu_in[(long long)n * C + g * 16 + t] - mean_ln) + cls[n - n0];
+        }
+        cf[512 + t] += add;
+      }
     }
   }
 }
@@ -679,6 +840,66 @@ __global__ void sw_bwd_weights(const float* __restrict__ wpart, int G, const flo
   const double ca = (double)a0 * a1 * da, cb = (double)b0 * b1 * db;
   if (dmean_w) { dmean_w[0] = (float)ca; dmean_w[1] = (float)-ca; }
   if (dvar_w) { dvar_w[0] = (float)cb; dvar_w[1] = (float)-cb; }
+}
+
+// The general softmax backward (sw_type 3 and 5, and the tied form of 2): with e_k the adjoint of
+// softmax output k relative to the instance component, dtheta_k = w_k (e_k - sum_j w_j e_j).  The
+// per-(n, g) differences are read from npart and summed in a fixed order by one wave.  Tied weights (var_w NULL):
+// the covariance side's gradient lands on sw_mean_weight as well.
+template <int SWT>
+__global__ void sw_bwd_weights_mix(const float* __restrict__ npart, int N, int G, const float* mean_w,
+                                   const float* var_w, float* dmean_w, float* dvar_w) {
+  // one wave: lane l adds rows l, l + 64, ... in order, then a fixed butterfly over the lanes
+  double ea = 0.0, fa = 0.0, el = 0.0, fl = 0.0, fz = 0.0;
+  for (int q = threadIdx.x; q < N * G; q += 64) {
+    const float* np = npart + (long long)q * SW_NP;
+    ea += np[304];
+    fa += np[305];
+    if constexpr (SWT != 2) {
+      el += np[306];
+      fl += np[307];
+      fz += np[308];
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ea += __shfl_xor(ea, o, 64);
+    fa += __shfl_xor(fa, o, 64);
+    if constexpr (SWT != 2) {
+      el += __shfl_xor(el, o, 64);
+      fl += __shfl_xor(fl, o, 64);
+      fz += __shfl_xor(fz, o, 64);
+    }
+  }
+  if (threadIdx.x != 0) return;
+  double e[5] = {ea, 0.0, 0.0, 0.0, 0.0}, f[5] = {fa, 0.0, 0.0, 0.0, 0.0};
+  if constexpr (SWT == 3) {
+    e[2] = el;
+    f[2] = fl;
+  }
+  if constexpr (SWT == 5) {
+    e[2] = ea;  // the BN / IN means are the BW / IW means
+    e[4] = el;
+    f[2] = f[3] = fz;  // v2, v3 weigh nothing
+    f[4] = fl;
+  }
+  float wa[SWT], wb[SWT];
+  sw_softmax<SWT>(mean_w, wa);
+  sw_softmax<SWT>(var_w ? var_w : mean_w, wb);
+  double se = 0.0, sf = 0.0;
+  for (int k = 0; k < SWT; ++k) {
+    se += (double)wa[k] * e[k];
+    sf += (double)wb[k] * f[k];
+  }
+  for (int k = 0; k < SWT; ++k) {
+    const double dm = (double)wa[k] * (e[k] - se), dv = (double)wb[k] * (f[k] - sf);
+    if (var_w) {
+      if (dmean_w) dmean_w[k] = (float)dm;
+      if (dvar_w) dvar_w[k] = (float)dv;
+    } else if (dmean_w) {
+      dmean_w[k] = (float)(dm + dv);
+    }
+  }
 }
 
 // dx_p = K ge_p + L (x_p - mu_n) + c ; thread = (pixel, group)
@@ -925,8 +1146,16 @@ extern "C" int dg_iw_cov_var(const float* fraw, int B, int C, float inv_hw1, flo
 
 extern "C" int64_t dg_sw_save_size(int N, int C) {
   if (N <= 0 || C <= 0 || C % SWC) return DG_ERR_INVALID;
-  const int64_t G = C / SWC;
-  return (2 * (int64_t)N * C + 2 * (int64_t)N * G * 256 + C + G * 256) * 4;
+  return sw_save_floats(N, C) * 4;
+}
+
+static inline bool sw_type_ok(int sw_type) { return sw_type == 2 || sw_type == 3 || sw_type == 5; }
+
+// sw_type 3 and 5 keep (mean_ln, var_ln) per instance behind the sw_type 2 layout
+extern "C" int64_t dg_swx_save_size(int N, int C, int sw_type) {
+  if (!sw_type_ok(sw_type)) return DG_ERR_INVALID;
+  const int64_t r = dg_sw_save_size(N, C);
+  return r < 0 || sw_type == 2 ? r : r + (int64_t)N * 2 * 4;
 }
 
 extern "C" int64_t dg_sw_moments_size(int C) {
@@ -943,7 +1172,7 @@ static int64_t sw_ws_core(int N, int HW, int C) {  // partials + coefficients, 8
   return (std::max(fwd, bwd) + 7) / 8 * 8;
 }
 
-// workspace of dg_sw_fwd/bwd (and of the split phases): core + one moments block
+// workspace of dg_sw_fwd/bwd (and of the split phases), every sw_type: core + one moments block
 extern "C" int64_t dg_sw_workspace(int N, int HW, int C) {
   if (N <= 0 || HW <= 0 || C <= 0 || C % SWC) return DG_ERR_INVALID;
   return sw_ws_core(N, HW, C) + (int64_t)(C / SWC) * SW_MOM * 8;
@@ -959,6 +1188,17 @@ extern "C" int64_t dg_sw_workspace(int N, int HW, int C) {
       hipLaunchKernelGGL((KERNEL<T, 4>), __VA_ARGS__);                                              \
   } while (0)
 
+// the small per-(instance, group) stages are compiled per sw_type (2: exactly the BW + IW code)
+#define SW_DISPATCH_T(SWT_, KERNEL, ...)                                                            \
+  do {                                                                                              \
+    if ((SWT_) == 2)                                                                                \
+      hipLaunchKernelGGL((KERNEL<2>), __VA_ARGS__);                                                 \
+    else if ((SWT_) == 3)                                                                           \
+      hipLaunchKernelGGL((KERNEL<3>), __VA_ARGS__);                                                 \
+    else                                                                                            \
+      hipLaunchKernelGGL((KERNEL<5>), __VA_ARGS__);                                                 \
+  } while (0)
+
 #define SW_CHECK_SHAPE(dtype, C, T_, ...)                                                           \
   do {                                                                                              \
     DG_REQUIRE(dtype == DG_F32 || DG_IS16(dtype));                                                \
@@ -967,10 +1207,8 @@ extern "C" int64_t dg_sw_workspace(int N, int HW, int C) {
     for (int64_t ld_ : {__VA_ARGS__}) DG_SUPPORTED(ld_ % V_ == 0);                                  \
   } while (0)
 
-// SwitchWhiten2d statistics, phase 1 (per rank): instance means/covariances into
-// `save` and the batch moments [G][272] doubles into `moments`.
-extern "C" int dg_sw_fwd_stats(int dtype, const void* x, int64_t ldx, int N, int HW, int C, float* save,
-                               double* moments, void* workspace, void* stream) {
+static int sw_fwd_stats_impl(int swt, int dtype, const void* x, int64_t ldx, int N, int HW, int C, float* save,
+                             double* moments, void* workspace, void* stream) {
   DG_REQUIRE(x && save && moments && workspace && N > 0 && HW > 0 && C > 0);
   SW_CHECK_SHAPE(dtype, C, 0, ldx);
   hipStream_t st = (hipStream_t)stream;
@@ -992,24 +1230,37 @@ extern "C" int dg_sw_fwd_stats(int dtype, const void* x, int64_t ldx, int N, int
   DG_CHECK_LAUNCH();
   hipLaunchKernelGGL(sw_inst_stats, dim3(G, N), dim3(256), 0, st, part, N, nb, HW, C, save);
   hipLaunchKernelGGL(sw_moments, dim3(G), dim3(256), 0, st, N, C, (const float*)save, moments);
+  if (swt != 2) hipLaunchKernelGGL(sw_ln_stats, dim3(N), dim3(256), 0, st, N, HW, C, save);
   DG_CHECK_LAUNCH();
   return DG_OK;
 }
 
-// Phase 2: batch statistics from `moments` summed over `count` images (all ranks),
-// running-stat update (training), whitening matrices, fused whiten+affine(+ReLU) apply.
-extern "C" int dg_sw_fwd_finish(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int T, float eps,
-                                float momentum, const float* mean_w, const float* var_w, const float* gamma,
-                                const float* beta, float* running_mean, float* running_cov, int training, int act,
-                                int64_t count, const double* moments, float* save, void* y, int64_t ldy,
-                                void* stream) {
-  DG_REQUIRE(x && y && save && moments && mean_w && var_w && running_mean && running_cov && count > 0);
+// SwitchWhiten2d statistics, phase 1 (per rank): instance means/covariances into
+// `save` and the batch moments [G][272] doubles into `moments`.
+extern "C" int dg_sw_fwd_stats(int dtype, const void* x, int64_t ldx, int N, int HW, int C, float* save,
+                               double* moments, void* workspace, void* stream) {
+  return sw_fwd_stats_impl(2, dtype, x, ldx, N, HW, C, save, moments, workspace, stream);
+}
+
+extern "C" int dg_swx_fwd_stats(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int sw_type,
+                                float* save, double* moments, void* workspace, void* stream) {
+  DG_REQUIRE(sw_type_ok(sw_type));
+  return sw_fwd_stats_impl(sw_type, dtype, x, ldx, N, HW, C, save, moments, workspace, stream);
+}
+
+static int sw_fwd_finish_impl(int swt, int tie, int dtype, const void* x, int64_t ldx, int N, int HW, int C, int T,
+                              float eps, float momentum, const float* mean_w, const float* var_w,
+                              const float* gamma, const float* beta, float* running_mean, float* running_cov,
+                              int training, int act, int64_t count, const double* moments, float* save, void* y,
+                              int64_t ldy, void* stream) {
+  DG_REQUIRE(x && y && save && moments && mean_w && (var_w || tie) && running_mean && running_cov && count > 0);
   DG_REQUIRE(N > 0 && HW > 0 && C > 0 && T >= 0 && (!gamma || beta));
   SW_CHECK_SHAPE(dtype, C, T, ldx, ldy);
   hipStream_t st = (hipStream_t)stream;
   const int G = C / SWC;
-  hipLaunchKernelGGL(sw_finalize, dim3(G, N), dim3(256), 0, st, moments, (double)count, N, C, T, eps, momentum, mean_w,
-                     var_w, gamma, beta, running_mean, running_cov, training, save);
+  if (tie) var_w = nullptr;
+  SW_DISPATCH_T(swt, sw_finalize, dim3(G, N), dim3(256), 0, st, moments, (double)count, N, C, T, eps, momentum,
+                mean_w, var_w, gamma, beta, running_mean, running_cov, training, save);
   DG_CHECK_LAUNCH();
   const float* aff = save + (int64_t)N * C + (int64_t)N * G * 256 + C + (int64_t)G * 256;
   const float* bias = aff + (int64_t)N * G * 256;
@@ -1045,6 +1296,27 @@ extern "C" int dg_sw_fwd_finish(int dtype, const void* x, int64_t ldx, int N, in
   return DG_OK;
 }
 
+// Phase 2: batch statistics from `moments` summed over `count` images (all ranks),
+// running-stat update (training), whitening matrices, fused whiten+affine(+ReLU) apply.
+extern "C" int dg_sw_fwd_finish(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int T, float eps,
+                                float momentum, const float* mean_w, const float* var_w, const float* gamma,
+                                const float* beta, float* running_mean, float* running_cov, int training, int act,
+                                int64_t count, const double* moments, float* save, void* y, int64_t ldy,
+                                void* stream) {
+  return sw_fwd_finish_impl(2, 0, dtype, x, ldx, N, HW, C, T, eps, momentum, mean_w, var_w, gamma, beta,
+                            running_mean, running_cov, training, act, count, moments, save, y, ldy, stream);
+}
+
+extern "C" int dg_swx_fwd_finish(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int sw_type, int tie,
+                                 int T, float eps, float momentum, const float* mean_w, const float* var_w,
+                                 const float* gamma, const float* beta, float* running_mean, float* running_cov,
+                                 int training, int act, int64_t count, const double* moments, float* save, void* y,
+                                 int64_t ldy, void* stream) {
+  DG_REQUIRE(sw_type_ok(sw_type));
+  return sw_fwd_finish_impl(sw_type, tie != 0, dtype, x, ldx, N, HW, C, T, eps, momentum, mean_w, var_w, gamma, beta,
+                            running_mean, running_cov, training, act, count, moments, save, y, ldy, stream);
+}
+
 // SwitchWhiten2d forward (sw_type 2), one rank: phase 1 + phase 2 with count = N.
 // The moments live at the end of the workspace.
 extern "C" int dg_sw_fwd(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int T, float eps,
@@ -1059,13 +1331,26 @@ extern "C" int dg_sw_fwd(int dtype, const void* x, int64_t ldx, int N, int HW, i
                           running_cov, training, act, N, moments, save, y, ldy, stream);
 }
 
-// Backward phase 1 (per rank): per-instance adjoints into the workspace, the batch
-// adjoints (dcov_bn, dmu_bn) into `bmoments` [G][272] doubles, dgamma/dbeta.
-extern "C" int dg_sw_bwd_stats(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
-                               int64_t ldx, int N, int HW, int C, int T, float eps, const float* mean_w,
-                               const float* var_w, const float* gamma, int act, const float* save, double* bmoments,
-                               float* dgamma, float* dbeta, void* workspace, void* stream) {
-  DG_REQUIRE(gy && x && save && bmoments && workspace && mean_w && var_w && (act == 0 || y));
+// Every argument is checked before the first launch: the finish phase's as well as the statistics'.
+extern "C" int dg_swx_fwd(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int sw_type, int tie, int T,
+                          float eps, float momentum, const float* mean_w, const float* var_w, const float* gamma,
+                          const float* beta, float* running_mean, float* running_cov, int training, int act,
+                          float* save, void* y, int64_t ldy, void* workspace, void* stream) {
+  DG_REQUIRE(sw_type_ok(sw_type) && workspace && N > 0 && HW > 0 && C > 0 && C % SWC == 0);
+  DG_REQUIRE(x && y && save && mean_w && (var_w || tie) && running_mean && running_cov && T >= 0 && (!gamma || beta));
+  SW_CHECK_SHAPE(dtype, C, T, ldx, ldy);
+  double* moments = (double*)((char*)workspace + sw_ws_core(N, HW, C));
+  int rc = sw_fwd_stats_impl(sw_type, dtype, x, ldx, N, HW, C, save, moments, workspace, stream);
+  if (rc) return rc;
+  return sw_fwd_finish_impl(sw_type, tie != 0, dtype, x, ldx, N, HW, C, T, eps, momentum, mean_w, var_w, gamma, beta,
+                            running_mean, running_cov, training, act, N, moments, save, y, ldy, stream);
+}
+
+static int sw_bwd_stats_impl(int swt, int tie, int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy,
+                             const void* x, int64_t ldx, int N, int HW, int C, int T, float eps, const float* mean_w,
+                             const float* var_w, const float* gamma, int act, const float* save, double* bmoments,
+                             float* dgamma, float* dbeta, void* workspace, void* stream) {
+  DG_REQUIRE(gy && x && save && bmoments && workspace && mean_w && (var_w || tie) && (act == 0 || y));
   DG_REQUIRE(N > 0 && HW > 0 && C > 0 && T >= 0);
   SW_CHECK_SHAPE(dtype, C, T, ldx, ldg, act ? ldy : ldx);
   hipStream_t st = (hipStream_t)stream;
@@ -1075,6 +1360,7 @@ extern "C" int dg_sw_bwd_stats(int dtype, const void* gy, int64_t ldg, const voi
   float* coef = part + (int64_t)N * nb * G * 272;
   float* wpart = coef + (int64_t)N * G * 528;
   float* npart = wpart + (int64_t)G * 4;
+  if (tie) var_w = nullptr;
   const size_t lds = (size_t)(2 * sw_pt(C) * (C + 16) + C) * 4;
   if (dtype == DG_BF16)
     SW_DISPATCH_G(sw_bwd_partial, bf16, dim3(nb, N), dim3(256), lds, st, (const bf16*)gy, ldg, (const bf16*)y, ldy,
@@ -1086,21 +1372,41 @@ extern "C" int dg_sw_bwd_stats(int dtype, const void* gy, int64_t ldg, const voi
     SW_DISPATCH_G(sw_bwd_partial, float, dim3(nb, N), dim3(256), lds, st, (const float*)gy, ldg, (const float*)y, ldy,
                   (const float*)x, ldx, HW, C, ppb, act, mu, part);
   DG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sw_bwd_small, dim3(G, N), dim3(256), 0, st, part, N, nb, HW, C, T, eps, mean_w, var_w, gamma,
-                     save, coef, npart);
+  SW_DISPATCH_T(swt, sw_bwd_small, dim3(G, N), dim3(256), 0, st, (const float*)part, N, nb, HW, C, T, eps, mean_w,
+                var_w, gamma, save, coef, npart);
   hipLaunchKernelGGL(sw_bwd_reduce, dim3(G), dim3(256), 0, st, (const float*)npart, N, C, bmoments, dgamma, dbeta,
                      wpart);
   DG_CHECK_LAUNCH();
   return DG_OK;
 }
 
-// Backward phase 2: batch adjoints summed over ranks (`count` images in total) ->
-// coefficients -> dx (+= when accumulate); mixing-weight gradients (this rank's part).
-extern "C" int dg_sw_bwd_finish(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
-                                int64_t ldx, int N, int HW, int C, int act, const float* mean_w, const float* var_w,
-                                const float* save, int64_t count, const double* bmoments, void* dx, int64_t lddx,
-                                int accumulate, float* dmean_w, float* dvar_w, void* workspace, void* stream) {
-  DG_REQUIRE(gy && x && dx && save && bmoments && workspace && mean_w && var_w && (act == 0 || y) && count > 0);
+// Backward phase 1 (per rank): per-instance adjoints into the workspace, the batch
+// adjoints (dcov_bn, dmu_bn) into `bmoments` [G][272] doubles, dgamma/dbeta.
+extern "C" int dg_sw_bwd_stats(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
+                               int64_t ldx, int N, int HW, int C, int T, float eps, const float* mean_w,
+                               const float* var_w, const float* gamma, int act, const float* save, double* bmoments,
+                               float* dgamma, float* dbeta, void* workspace, void* stream) {
+  return sw_bwd_stats_impl(2, 0, dtype, gy, ldg, y, ldy, x, ldx, N, HW, C, T, eps, mean_w, var_w, gamma, act, save,
+                           bmoments, dgamma, dbeta, workspace, stream);
+}
+
+extern "C" int dg_swx_bwd_stats(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
+                                int64_t ldx, int N, int HW, int C, int sw_type, int tie, int T, float eps,
+                                const float* mean_w, const float* var_w, const float* gamma, int act,
+                                const float* save, double* bmoments, float* dgamma, float* dbeta, void* workspace,
+                                void* stream) {
+  DG_REQUIRE(sw_type_ok(sw_type));
+  return sw_bwd_stats_impl(sw_type, tie != 0, dtype, gy, ldg, y, ldy, x, ldx, N, HW, C, T, eps, mean_w, var_w, gamma,
+                           act, save, bmoments, dgamma, dbeta, workspace, stream);
+}
+
+static int sw_bwd_finish_impl(int swt, int tie, int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy,
+                              const void* x, int64_t ldx, int N, int HW, int C, int act, const float* mean_w,
+                              const float* var_w, const float* save, int64_t count, const double* bmoments, void* dx,
+                              int64_t lddx, int accumulate, float* dmean_w, float* dvar_w, void* workspace,
+                              void* stream) {
+  DG_REQUIRE(gy && x && dx && save && bmoments && workspace && mean_w && (var_w || tie) && (act == 0 || y) &&
+             count > 0);
   DG_REQUIRE(N > 0 && HW > 0 && C > 0);
   SW_CHECK_SHAPE(dtype, C, 0, ldx, ldg, lddx, act ? ldy : ldx);
   hipStream_t st = (hipStream_t)stream;
@@ -1109,9 +1415,15 @@ extern "C" int dg_sw_bwd_finish(int dtype, const void* gy, int64_t ldg, const vo
   float* part = (float*)workspace;
   float* coef = part + (int64_t)N * nb * G * 272;
   float* wpart = coef + (int64_t)N * G * 528;
-  hipLaunchKernelGGL(sw_bwd_coef, dim3(G), dim3(256), 0, st, bmoments, (double)count, N, HW, C, save, coef);
+  const float* npart = wpart + (int64_t)G * 4;
+  if (tie) var_w = nullptr;
+  SW_DISPATCH_T(swt, sw_bwd_coef, dim3(G), dim3(256), 0, st, bmoments, (double)count, N, HW, C, save, npart, coef);
   DG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sw_bwd_weights, dim3(1), dim3(64), 0, st, wpart, G, mean_w, var_w, dmean_w, dvar_w);
+  if (swt == 2 && !tie)
+    hipLaunchKernelGGL(sw_bwd_weights, dim3(1), dim3(64), 0, st, (const float*)wpart, G, mean_w, var_w, dmean_w,
+                       dvar_w);
+  else
+    SW_DISPATCH_T(swt, sw_bwd_weights_mix, dim3(1), dim3(64), 0, st, npart, N, G, mean_w, var_w, dmean_w, dvar_w);
   DG_CHECK_LAUNCH();
   if (sw_apply_mfma_on()) {
     const int mnb = sw_apply_nb(HW, N);
@@ -1146,6 +1458,26 @@ extern "C" int dg_sw_bwd_finish(int dtype, const void* gy, int64_t ldg, const vo
   return DG_OK;
 }
 
+// Backward phase 2: batch adjoints summed over ranks (`count` images in total) ->
+// coefficients -> dx (+= when accumulate); mixing-weight gradients (this rank's part).
+extern "C" int dg_sw_bwd_finish(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
+                                int64_t ldx, int N, int HW, int C, int act, const float* mean_w, const float* var_w,
+                                const float* save, int64_t count, const double* bmoments, void* dx, int64_t lddx,
+                                int accumulate, float* dmean_w, float* dvar_w, void* workspace, void* stream) {
+  return sw_bwd_finish_impl(2, 0, dtype, gy, ldg, y, ldy, x, ldx, N, HW, C, act, mean_w, var_w, save, count, bmoments,
+                            dx, lddx, accumulate, dmean_w, dvar_w, workspace, stream);
+}
+
+extern "C" int dg_swx_bwd_finish(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
+                                 int64_t ldx, int N, int HW, int C, int sw_type, int tie, int act,
+                                 const float* mean_w, const float* var_w, const float* save, int64_t count,
+                                 const double* bmoments, void* dx, int64_t lddx, int accumulate, float* dmean_w,
+                                 float* dvar_w, void* workspace, void* stream) {
+  DG_REQUIRE(sw_type_ok(sw_type));
+  return sw_bwd_finish_impl(sw_type, tie != 0, dtype, gy, ldg, y, ldy, x, ldx, N, HW, C, act, mean_w, var_w, save,
+                            count, bmoments, dx, lddx, accumulate, dmean_w, dvar_w, workspace, stream);
+}
+
 // Backward of dg_sw_fwd (training mode, one rank): phase 1 + phase 2 with count = N.
 extern "C" int dg_sw_bwd(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
                          int64_t ldx, int N, int HW, int C, int T, float eps, const float* mean_w,
@@ -1159,4 +1491,20 @@ extern "C" int dg_sw_bwd(int dtype, const void* gy, int64_t ldg, const void* y, 
   if (rc) return rc;
   return dg_sw_bwd_finish(dtype, gy, ldg, y, ldy, x, ldx, N, HW, C, act, mean_w, var_w, save, N, bm, dx, lddx,
                           accumulate, dmean_w, dvar_w, workspace, stream);
+}
+
+extern "C" int dg_swx_bwd(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
+                          int64_t ldx, int N, int HW, int C, int sw_type, int tie, int T, float eps,
+                          const float* mean_w, const float* var_w, const float* gamma, int act, const float* save,
+                          void* dx, int64_t lddx, int accumulate, float* dgamma, float* dbeta, float* dmean_w,
+                          float* dvar_w, void* workspace, void* stream) {
+  DG_REQUIRE(sw_type_ok(sw_type) && workspace && N > 0 && HW > 0 && C > 0 && C % SWC == 0);
+  DG_REQUIRE(gy && x && dx && save && mean_w && (var_w || tie) && (act == 0 || y) && T >= 0);
+  SW_CHECK_SHAPE(dtype, C, T, ldx, ldg, lddx, act ? ldy : ldx);
+  double* bm = (double*)((char*)workspace + sw_ws_core(N, HW, C));
+  int rc = sw_bwd_stats_impl(sw_type, tie != 0, dtype, gy, ldg, y, ldy, x, ldx, N, HW, C, T, eps, mean_w, var_w,
+                             gamma, act, save, bm, dgamma, dbeta, workspace, stream);
+  if (rc) return rc;
+  return sw_bwd_finish_impl(sw_type, tie != 0, dtype, gy, ldg, y, ldy, x, ldx, N, HW, C, act, mean_w, var_w, save, N,
+                            bm, dx, lddx, accumulate, dmean_w, dvar_w, workspace, stream);
 }

@@ -1111,65 +1111,97 @@ def iw_cluster_mask(v: torch.Tensor, sorted: torch.Tensor, bounds: torch.Tensor,
     return mask, ns
 
 
+def _sw_plain(sw_type, tie, gamma) -> bool:
+    """The SW counter's own configuration (sw_type 2, untied, affine): the dg_sw_* entry points."""
+    if sw_type not in (2, 3, 5):
+        raise DGError(f"sw_type should be in [2, 3, 5], but got {sw_type}")
+    return sw_type == 2 and not tie and gamma is not None
+
+
+def _sw_save(x: Act, sw_type: int) -> torch.Tensor:
+    nbytes = query("dg_sw_save_size", x.N, x.C) if sw_type == 2 else query("dg_swx_save_size", x.N, x.C, sw_type)
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=x.buf.device)
+
+
 def sw_fwd(x: Act, mean_w, var_w, gamma, beta, running_mean, running_cov, training: bool,
-           act: int, y: Act, T: int = 5, eps: float = 1e-5, momentum: float = 0.9) -> torch.Tensor:
-    """SwitchWhiten2d (sw_type 2) forward; returns the `save` statistics buffer."""
+           act: int, y: Act, T: int = 5, eps: float = 1e-5, momentum: float = 0.9, sw_type: int = 2,
+           tie: bool = False) -> torch.Tensor:
+    """SwitchWhiten2d forward; returns the `save` statistics buffer.  sw_type 2 / 3 / 5; tie:
+    tie_weight (var_w may be None); gamma = beta = None: affine=False."""
     HW = x.H * x.W
-    save = torch.empty(query("dg_sw_save_size", x.N, x.C) // 4, dtype=torch.float32,
-                       device=x.buf.device)
+    plain = _sw_plain(sw_type, tie, gamma)
+    save = _sw_save(x, sw_type)
     ws = query("dg_sw_workspace", x.N, HW, x.C)
     work = torch.empty(ws // 4 + 1, dtype=torch.float32, device=x.buf.device)
-    call("dg_sw_fwd", x.dt, x.ptr, x.ld, x.N, HW, x.C, int(T), float(eps), float(momentum),
-         ptr(mean_w), ptr(var_w), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_cov),
-         int(training), act, ptr(save), y.ptr, y.ld, ptr(work), stream())
+    if plain:
+        call("dg_sw_fwd", x.dt, x.ptr, x.ld, x.N, HW, x.C, int(T), float(eps), float(momentum),
+             ptr(mean_w), ptr(var_w), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_cov),
+             int(training), act, ptr(save), y.ptr, y.ld, ptr(work), stream())
+    else:
+        call("dg_swx_fwd", x.dt, x.ptr, x.ld, x.N, HW, x.C, int(sw_type), int(tie), int(T), float(eps),
+             float(momentum), ptr(mean_w), ptr(var_w), ptr(gamma), ptr(beta), ptr(running_mean),
+             ptr(running_cov), int(training), act, ptr(save), y.ptr, y.ld, ptr(work), stream())
     return save
 
 
 def sw_fwd_sync(x: Act, mean_w, var_w, gamma, beta, running_mean, running_cov, training: bool,
-                act: int, y: Act, reduce_fn, T: int = 5, eps: float = 1e-5, momentum: float = 0.9):
+                act: int, y: Act, reduce_fn, T: int = 5, eps: float = 1e-5, momentum: float = 0.9,
+                sw_type: int = 2, tie: bool = False):
     """SyncSwitchWhiten2d forward: reduce_fn(moments f64 tensor) -> (moments summed over ranks,
     total image count) sits between the statistics and the whitening phases.
     Returns (save, workspace) for sw_bwd_sync."""
     HW = x.H * x.W
     dev = x.buf.device
-    save = torch.empty(query("dg_sw_save_size", x.N, x.C) // 4, dtype=torch.float32, device=dev)
+    plain = _sw_plain(sw_type, tie, gamma)
+    save = _sw_save(x, sw_type)
     ws = query("dg_sw_workspace", x.N, HW, x.C)
     work = torch.empty(ws // 4 + 1, dtype=torch.float32, device=dev)
     mom = torch.empty(query("dg_sw_moments_size", x.C) // 8, dtype=torch.float64, device=dev)
     count = x.N
-    if training:
+    if plain:
         call("dg_sw_fwd_stats", x.dt, x.ptr, x.ld, x.N, HW, x.C, ptr(save), ptr(mom), ptr(work), stream())
-        mom, count = reduce_fn(mom)
     else:
-        call("dg_sw_fwd_stats", x.dt, x.ptr, x.ld, x.N, HW, x.C, ptr(save), ptr(mom), ptr(work), stream())
-    call("dg_sw_fwd_finish", x.dt, x.ptr, x.ld, x.N, HW, x.C, int(T), float(eps), float(momentum),
-         ptr(mean_w), ptr(var_w), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_cov),
-         int(training), act, int(count), ptr(mom), ptr(save), y.ptr, y.ld, stream())
+        call("dg_swx_fwd_stats", x.dt, x.ptr, x.ld, x.N, HW, x.C, int(sw_type), ptr(save), ptr(mom),
+             ptr(work), stream())
+    if training:
+        mom, count = reduce_fn(mom)
+    if plain:
+        call("dg_sw_fwd_finish", x.dt, x.ptr, x.ld, x.N, HW, x.C, int(T), float(eps), float(momentum),
+             ptr(mean_w), ptr(var_w), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_cov),
+             int(training), act, int(count), ptr(mom), ptr(save), y.ptr, y.ld, stream())
+    else:
+        call("dg_swx_fwd_finish", x.dt, x.ptr, x.ld, x.N, HW, x.C, int(sw_type), int(tie), int(T),
+             float(eps), float(momentum), ptr(mean_w), ptr(var_w), ptr(gamma), ptr(beta),
+             ptr(running_mean), ptr(running_cov), int(training), act, int(count), ptr(mom), ptr(save),
+             y.ptr, y.ld, stream())
     return save, work, count
 
 
 def sw_bwd_sync(gy: Act, y: Act | None, x: Act, save, work, mean_w, var_w, gamma, act: int, dx: Act,
                 reduce_fn, dgamma=None, dbeta=None, dmean_w=None, dvar_w=None, accumulate=False,
-                T: int = 5, eps: float = 1e-5):
+                T: int = 5, eps: float = 1e-5, sw_type: int = 2, tie: bool = False):
     HW = x.H * x.W
+    ex = () if _sw_plain(sw_type, tie, gamma) else (int(sw_type), int(tie))
+    pre = "dg_swx_" if ex else "dg_sw_"
+    yp, yl = (y.ptr, y.ld) if y is not None else (None, 0)
     bm = torch.empty(query("dg_sw_moments_size", x.C) // 8, dtype=torch.float64, device=x.buf.device)
-    call("dg_sw_bwd_stats", x.dt, gy.ptr, gy.ld, y.ptr if y is not None else None,
-         y.ld if y is not None else 0, x.ptr, x.ld, x.N, HW, x.C, int(T), float(eps), ptr(mean_w),
-         ptr(var_w), ptr(gamma), act, ptr(save), ptr(bm), ptr(dgamma), ptr(dbeta), ptr(work), stream())
+    call(pre + "bwd_stats", x.dt, gy.ptr, gy.ld, yp, yl, x.ptr, x.ld, x.N, HW, x.C, *ex, int(T),
+         float(eps), ptr(mean_w), ptr(var_w), ptr(gamma), act, ptr(save), ptr(bm), ptr(dgamma),
+         ptr(dbeta), ptr(work), stream())
     bm, count = reduce_fn(bm)
-    call("dg_sw_bwd_finish", x.dt, gy.ptr, gy.ld, y.ptr if y is not None else None,
-         y.ld if y is not None else 0, x.ptr, x.ld, x.N, HW, x.C, act, ptr(mean_w), ptr(var_w),
-         ptr(save), int(count), ptr(bm), dx.ptr, dx.ld, int(accumulate), ptr(dmean_w), ptr(dvar_w),
-         ptr(work), stream())
+    call(pre + "bwd_finish", x.dt, gy.ptr, gy.ld, yp, yl, x.ptr, x.ld, x.N, HW, x.C, *ex, act,
+         ptr(mean_w), ptr(var_w), ptr(save), int(count), ptr(bm), dx.ptr, dx.ld, int(accumulate),
+         ptr(dmean_w), ptr(dvar_w), ptr(work), stream())
 
 
 def sw_bwd(gy: Act, y: Act | None, x: Act, save, mean_w, var_w, gamma, act: int, dx: Act,
            dgamma=None, dbeta=None, dmean_w=None, dvar_w=None, accumulate=False, T: int = 5,
-           eps: float = 1e-5):
+           eps: float = 1e-5, sw_type: int = 2, tie: bool = False):
     HW = x.H * x.W
+    ex = () if _sw_plain(sw_type, tie, gamma) else (int(sw_type), int(tie))
     ws = query("dg_sw_workspace", x.N, HW, x.C)
     work = torch.empty(ws // 4 + 1, dtype=torch.float32, device=x.buf.device)
-    call("dg_sw_bwd", x.dt, gy.ptr, gy.ld, y.ptr if y is not None else None,
-         y.ld if y is not None else 0, x.ptr, x.ld, x.N, HW, x.C, int(T), float(eps), ptr(mean_w),
+    call("dg_swx_bwd" if ex else "dg_sw_bwd", x.dt, gy.ptr, gy.ld, y.ptr if y is not None else None,
+         y.ld if y is not None else 0, x.ptr, x.ld, x.N, HW, x.C, *ex, int(T), float(eps), ptr(mean_w),
          ptr(var_w), ptr(gamma), act, ptr(save), dx.ptr, dx.ld, int(accumulate), ptr(dgamma),
          ptr(dbeta), ptr(dmean_w), ptr(dvar_w), ptr(work), stream())

@@ -27,7 +27,9 @@ import warnings
 import torch
 import torch.nn as nn
 
+from .. import dist as D
 from .. import engine as E
+from .. import kernels as K
 from .. import trunk as TR
 from .models import _DGBase
 
@@ -173,9 +175,68 @@ class IBNCounter_ResNet(_CounterBase):
 # ---------------------------------------------------------------------------
 # Switchable Whitening
 # ---------------------------------------------------------------------------
+class _SwitchWhitenFn(torch.autograd.Function):
+    """SwitchWhiten2d.forward outside the trunk plan: one autograd node over the SW kernels, NCHW at
+    the boundary (the kernels read NHWC).  Absent parameters (tied weights, no affine) arrive as None."""
+
+    @staticmethod
+    def forward(ctx, x, mean_w, var_w, gamma, beta, m):
+        if x.dim() != 4 or not x.is_cuda or not x.is_floating_point():
+            raise K.DGError("SwitchWhiten2d.forward expects an NCHW floating-point tensor on the GPU")
+        if x.shape[1] != m.num_features:
+            raise K.DGError(f"SwitchWhiten2d({m.num_features}): input has {x.shape[1]} channels")
+        xa = K.Act(x.detach().permute(0, 2, 3, 1).contiguous())
+        ya = K.Act(torch.empty_like(xa.buf))
+        par = tuple(_SwitchWhitenFn._f32(t) for t in (mean_w, var_w, gamma, beta))
+        ctx.kw = dict(T=m.T, eps=m.eps, sw_type=m.sw_type, tie=m.tie_weight)
+        ctx.training = m.training
+        ctx.sync = m.training and getattr(m, "sync", False) and D.world() > 1
+        if ctx.sync:
+            save, _, _ = K.sw_fwd_sync(xa, *par, m.running_mean, m.running_cov, True, 0, ya,
+                                       D.sum_moments(xa.N), momentum=m.momentum, **ctx.kw)
+        else:
+            save = K.sw_fwd(xa, *par, m.running_mean, m.running_cov, m.training, 0, ya, momentum=m.momentum,
+                            **ctx.kw)
+        # the parameters themselves are saved (not their f32 views), so that autograd's version check
+        # sees a parameter written in place between forward and backward
+        ctx.save_for_backward(xa.buf, save, mean_w, var_w, gamma)
+        return ya.buf.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def _f32(t):
+        return None if t is None else t.detach().float().contiguous()
+
+    @staticmethod
+    def backward(ctx, gy):
+        xbuf, save, mean_w, var_w, gamma = ctx.saved_tensors
+        ptypes = tuple(None if t is None else t.dtype for t in (mean_w, var_w, gamma, gamma))
+        mean_w, var_w, gamma = (_SwitchWhitenFn._f32(t) for t in (mean_w, var_w, gamma))
+        xa = K.Act(xbuf)
+        dev = xbuf.device
+        ga = K.Act(gy.permute(0, 2, 3, 1).contiguous().to(xbuf.dtype))
+        dxa = K.Act(torch.empty_like(xbuf))
+        new = lambda t: None if t is None else torch.empty(t.shape, dtype=torch.float32, device=dev)  # noqa: E731
+        dmw, dvw, dgam = new(mean_w), new(var_w), new(gamma)
+        dbet = new(gamma)
+        if ctx.sync or not ctx.training:
+            # eval: the batch statistics are the running statistics, constants of the graph, so the batch
+            # adjoints (bmoments) the finish phase adds are zero; every other term is per instance
+            work = torch.empty(K.query("dg_sw_workspace", xa.N, xa.H * xa.W, xa.C) // 4 + 1, dtype=torch.float32,
+                               device=dev)
+            reduce_fn = D.sum_moments(xa.N) if ctx.sync else (lambda bm: (torch.zeros_like(bm), xa.N))
+            K.sw_bwd_sync(ga, None, xa, save, work, mean_w, var_w, gamma, 0, dxa, reduce_fn, dgam, dbet, dmw, dvw,
+                          **ctx.kw)
+        else:
+            K.sw_bwd(ga, None, xa, save, mean_w, var_w, gamma, 0, dxa, dgam, dbet, dmw, dvw, **ctx.kw)
+        grads = [None if g is None else g.to(dt) for g, dt in zip((dmw, dvw, dgam, dbet), ptypes)]
+        return (dxa.buf.permute(0, 3, 1, 2), *grads, None)
+
+
 class SwitchWhiten2d(nn.Module):
-    """Parameters/buffers of models/SW/ops/switchwhiten.py:7-81 (sw_type 2 only on the
-    HIP path); the computation is dg_sw_fwd / dg_sw_bwd inside the trunk plan."""
+    """models/SW/ops/switchwhiten.py:7-183 on the HIP kernels: sw_type 2 (BW + IW), 3 (+ LN) and
+    5 (+ BN + IN + LN), tied or separate mixing weights, with or without the affine; groups of 16
+    channels.  The trunk plan calls the kernels directly; forward() is the same computation as one
+    autograd node for use in any other network."""
 
     def __init__(self, num_features, num_pergroup=16, sw_type=2, T=5, tie_weight=False, eps=1e-5,
                  momentum=0.99, affine=True):
@@ -183,18 +244,24 @@ class SwitchWhiten2d(nn.Module):
         if sw_type not in [2, 3, 5]:
             raise ValueError("sw_type should be in [2, 3, 5], but got {}".format(sw_type))
         assert num_features % num_pergroup == 0
-        if sw_type != 2 or num_pergroup != 16 or tie_weight or not affine:
-            raise NotImplementedError("HIP SwitchWhiten2d: sw_type=2, num_pergroup=16, "
-                                      "tie_weight=False, affine=True (the SW counter's sw_cfg)")
+        if num_pergroup != 16:
+            raise NotImplementedError("HIP SwitchWhiten2d: num_pergroup=16 (the whitening kernels' group)")
         self.num_features = num_features
         self.num_pergroup = num_pergroup
         self.num_groups = num_features // num_pergroup
         self.sw_type, self.T, self.tie_weight = sw_type, T, tie_weight
         self.eps, self.momentum, self.affine = eps, momentum, affine
         self.sw_mean_weight = nn.Parameter(torch.ones(sw_type))
-        self.sw_var_weight = nn.Parameter(torch.ones(sw_type))
-        self.weight = nn.Parameter(torch.ones(num_features))
-        self.bias = nn.Parameter(torch.zeros(num_features))
+        if not tie_weight:
+            self.sw_var_weight = nn.Parameter(torch.ones(sw_type))
+        else:
+            self.register_parameter("sw_var_weight", None)
+        if affine:
+            self.weight = nn.Parameter(torch.ones(num_features))
+            self.bias = nn.Parameter(torch.zeros(num_features))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
         self.register_buffer("running_mean", torch.zeros(self.num_groups, num_pergroup, 1))
         self.register_buffer("running_cov",
                              torch.eye(num_pergroup).unsqueeze(0).repeat(self.num_groups, 1, 1))
@@ -204,9 +271,18 @@ class SwitchWhiten2d(nn.Module):
         self.running_mean.zero_()
         self.running_cov.zero_()  # as the reference (switchwhiten.py:66-67)
         nn.init.ones_(self.sw_mean_weight)
-        nn.init.ones_(self.sw_var_weight)
-        nn.init.ones_(self.weight)
-        nn.init.zeros_(self.bias)
+        if not self.tie_weight:
+            nn.init.ones_(self.sw_var_weight)
+        if self.affine:
+            nn.init.ones_(self.weight)
+            nn.init.zeros_(self.bias)
+
+    def extra_repr(self):
+        return ("{num_features}, num_pergroup={num_pergroup}, sw_type={sw_type}, T={T}, tie_weight={tie_weight}, "
+                "eps={eps}, momentum={momentum}, affine={affine}".format(**self.__dict__))
+
+    def forward(self, x):
+        return _SwitchWhitenFn.apply(x, self.sw_mean_weight, self.sw_var_weight, self.weight, self.bias, self)
 
 
 class SyncSwitchWhiten2d(SwitchWhiten2d):
@@ -225,23 +301,26 @@ class SyncSwitchWhiten2d(SwitchWhiten2d):
 SW_CFG = dict(type="SW", sw_type=2, num_pergroup=16, T=5, tie_weight=False, momentum=0.9, affine=True)
 
 
-def _make_sw(sync=False):
+def _make_sw(sync=False, sw_cfg=None):
+    """The layer factory of SW/backbones/resnet.py's build_norm_layer: sw_cfg merged over SW_CFG."""
     cls = SyncSwitchWhiten2d if sync else SwitchWhiten2d
-    return lambda c: cls(c, num_pergroup=16, sw_type=2, T=5, tie_weight=False, eps=1e-5,
-                         momentum=0.9, affine=True)
+    cfg = dict(SW_CFG, **(sw_cfg or {}))
+    cfg.pop("type")
+    cfg.setdefault("eps", 1e-5)
+    return lambda c: cls(c, **cfg)
 
 
 class Bottleneck_SW(nn.Module):
     """SW/backbones/resnet.py:75-118: norm2 is SwitchWhiten2d ('sw2') when with_sw."""
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, with_sw=False, sync=False):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, with_sw=False, sync=False, sw_cfg=None):
         super().__init__()
         self.norm2_name = "sw2" if with_sw else "bn2"
         self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=1, bias=False)
         self.add_module("bn1", nn.BatchNorm2d(planes))
         self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
-        self.add_module(self.norm2_name, _make_sw(sync)(planes) if with_sw else nn.BatchNorm2d(planes))
+        self.add_module(self.norm2_name, _make_sw(sync, sw_cfg)(planes) if with_sw else nn.BatchNorm2d(planes))
         self.conv3 = nn.Conv2d(planes, planes * 4, kernel_size=1, bias=False)
         self.add_module("bn3", nn.BatchNorm2d(planes * 4))
         self.relu = nn.ReLU(inplace=True)
@@ -256,10 +335,10 @@ class Bottleneck_SW(nn.Module):
                         ds[1] if ds is not None else None)
 
 
-def _sw_backbone(sync=False):
+def _sw_backbone(sync=False, sw_cfg=None):
     """children()[:7] of SW resnet50(sw_cfg): conv1, sw1, relu, maxpool, layer1-3."""
     conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
-    mods = [conv1, _make_sw(sync)(64), nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2, padding=1)]
+    mods = [conv1, _make_sw(sync, sw_cfg)(64), nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2, padding=1)]
     inplanes = 64
     for planes, nblk, stride in LAYERS[:3]:
         ds = None
@@ -268,7 +347,7 @@ def _sw_backbone(sync=False):
         blocks = [Bottleneck_SW(inplanes, planes, stride, ds, with_sw=False)]
         inplanes = planes * 4
         for i in range(1, nblk):
-            blocks.append(Bottleneck_SW(inplanes, planes, with_sw=(i % 2 == 1), sync=sync))
+            blocks.append(Bottleneck_SW(inplanes, planes, with_sw=(i % 2 == 1), sync=sync, sw_cfg=sw_cfg))
         mods.append(nn.Sequential(*blocks))
     bb = nn.Sequential(*mods)
     for m in bb.modules():
@@ -283,12 +362,13 @@ def _sw_backbone(sync=False):
 class SWCounter_ResNet(_CounterBase):
     """models/SW/__init__.py:24-42.  sync=True builds SyncSwitchWhiten2d layers (batch
     whitening statistics shared over the data-parallel ranks; an extension — the
-    reference's SW counter uses SwitchWhiten2d)."""
+    reference's SW counter uses SwitchWhiten2d).  sw_cfg: a dict merged over SW_CFG, e.g.
+    {'sw_type': 5} for the five-normaliser form (SW/backbones/resnet.py's sw_cfg)."""
 
-    def __init__(self, pretrained=True, sync=False):
+    def __init__(self, pretrained=True, sync=False, sw_cfg=None):
         super().__init__()
         self._init_precision()
-        self.backbone = _sw_backbone(sync)
+        self.backbone = _sw_backbone(sync, sw_cfg)
         _load_local(self.backbone, "resnet50", pretrained)
         self.head = _counter_head()
         self._plan = None

@@ -158,7 +158,7 @@ class Norm:
         if self.kind == "bn" or (self.kind == "in" and m is not None and m.affine):
             return [m.weight, m.bias]
         if self.kind == "sw":
-            return [m.sw_mean_weight, m.sw_var_weight, m.weight, m.bias]
+            return [p for p in (m.sw_mean_weight, m.sw_var_weight, m.weight, m.bias) if p is not None]
         return []
 
     def _in_affine(self):
@@ -177,15 +177,19 @@ class Norm:
             K.instnorm_apply(z, st, g, b, act, y)
             return st
         m = self.m  # sw
+        mw, vw, gam, bet = self._sw_params()
+        kw = dict(T=m.T, eps=m.eps, momentum=m.momentum, sw_type=m.sw_type, tie=m.tie_weight)
         if getattr(m, "sync", False) and D.world() > 1:  # SyncSwitchWhiten2d over RCCL
-            save, work, _ = K.sw_fwd_sync(z, m.sw_mean_weight.detach(), m.sw_var_weight.detach(),
-                                          m.weight.detach(), m.bias.detach(), m.running_mean,
-                                          m.running_cov, training, act, y, D.sum_moments(z.N), T=m.T,
-                                          eps=m.eps, momentum=m.momentum)
+            save, work, _ = K.sw_fwd_sync(z, mw, vw, gam, bet, m.running_mean, m.running_cov, training, act, y,
+                                          D.sum_moments(z.N), **kw)
             return ("sync", save, work)
-        return K.sw_fwd(z, m.sw_mean_weight.detach(), m.sw_var_weight.detach(), m.weight.detach(),
-                        m.bias.detach(), m.running_mean, m.running_cov, training, act, y, T=m.T,
-                        eps=m.eps, momentum=m.momentum)
+        return K.sw_fwd(z, mw, vw, gam, bet, m.running_mean, m.running_cov, training, act, y, **kw)
+
+    def _sw_params(self):
+        """(sw_mean_weight, sw_var_weight, weight, bias) detached; None where the module has none
+        (tie_weight, affine=False)."""
+        m = self.m
+        return tuple(None if p is None else p.detach() for p in (m.sw_mean_weight, m.sw_var_weight, m.weight, m.bias))
 
     def backward(self, g: Act, z: Act, y: Act, st, act: int, dz: Act, grads: dict):
         """dz = d norm / dz given g = dL/dy (ReLU mask from y when act)."""
@@ -207,19 +211,20 @@ class Norm:
                 K.instnorm_bwd(g, z, st, None, dz)
         else:
             m = self.m
-            d = {p: torch.empty(p.shape, dtype=torch.float32, device=dev)
-                 for p in (m.weight, m.bias, m.sw_mean_weight, m.sw_var_weight)}
+            ps = (m.weight, m.bias, m.sw_mean_weight, m.sw_var_weight)
+            dg, db, dmw, dvw = (None if p is None else torch.empty(p.shape, dtype=torch.float32, device=dev)
+                                for p in ps)
+            mw, vw, gam, _ = self._sw_params()
+            kw = dict(T=m.T, eps=m.eps, sw_type=m.sw_type, tie=m.tie_weight)
             if isinstance(st, tuple):  # synchronized statistics: all-reduce the batch adjoints
                 _, save, work = st
-                K.sw_bwd_sync(g, y, z, save, work, m.sw_mean_weight.detach(), m.sw_var_weight.detach(),
-                              m.weight.detach(), act, dz, D.sum_moments(z.N), d[m.weight], d[m.bias],
-                              d[m.sw_mean_weight], d[m.sw_var_weight], T=m.T, eps=m.eps)
+                K.sw_bwd_sync(g, y, z, save, work, mw, vw, gam, act, dz, D.sum_moments(z.N), dg, db, dmw, dvw,
+                              **kw)
             else:
-                K.sw_bwd(g, y, z, st, m.sw_mean_weight.detach(), m.sw_var_weight.detach(),
-                         m.weight.detach(), act, dz, d[m.weight], d[m.bias], d[m.sw_mean_weight],
-                         d[m.sw_var_weight], T=m.T, eps=m.eps)
-            for p, v in d.items():
-                _acc(grads, p, v)
+                K.sw_bwd(g, y, z, st, mw, vw, gam, act, dz, dg, db, dmw, dvw, **kw)
+            for p, v in zip(ps, (dg, db, dmw, dvw)):
+                if p is not None:
+                    _acc(grads, p, v)
 
 
 class Block:

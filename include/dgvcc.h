@@ -512,6 +512,44 @@ int dg_sw_bwd(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy
               const float* var_w, const float* gamma, int act, const float* save, void* dx,
               int64_t lddx, int accumulate, float* dgamma, float* dbeta, float* dmean_w,
               float* dvar_w, void* workspace, void* stream);
+/* SwitchWhiten2d with sw_type 2 (BW + IW), 3 (+ LN) or 5 (+ BN + IN + LN) and the operator's other
+ * switches (switchwhiten.py:126-164): the dg_sw_* entry points above with `sw_type` and `tie` after C.
+ * mean_w / var_w hold sw_type floats.  tie != 0 is tie_weight: the covariance side mixes with
+ * softmax(mean_w), var_w and dvar_w are not read (may be NULL), and dmean_w receives both sides'
+ * gradient.  gamma == beta == NULL is affine=False (y = W (x - mean)); dgamma / dbeta NULL then.
+ * LN's mean and unbiased variance are per-instance statistics of the input, in eval mode too; BN's
+ * variance is the diagonal of the (all-reduced) batch covariance, so the moments [G][272] exchanged
+ * between the split phases are those of sw_type 2.  `save` takes dg_swx_save_size bytes (sw_type 2:
+ * dg_sw_save_size), the workspace dg_sw_workspace bytes; a stats/finish pair and a forward/backward
+ * pair use one sw_type and tie.  With sw_type 2, tie 0 and an affine the results equal dg_sw_*'s bit
+ * for bit.  Another sw_type is DG_ERR_INVALID; every argument is checked before the first launch. */
+int64_t dg_swx_save_size(int N, int C, int sw_type);
+int dg_swx_fwd(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int sw_type, int tie, int T,
+               float eps, float momentum, const float* mean_w, const float* var_w, const float* gamma,
+               const float* beta, float* running_mean, float* running_cov, int training, int act,
+               float* save, void* y, int64_t ldy, void* workspace, void* stream);
+int dg_swx_fwd_stats(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int sw_type,
+                     float* save, double* moments, void* workspace, void* stream);
+int dg_swx_fwd_finish(int dtype, const void* x, int64_t ldx, int N, int HW, int C, int sw_type, int tie,
+                      int T, float eps, float momentum, const float* mean_w, const float* var_w,
+                      const float* gamma, const float* beta, float* running_mean, float* running_cov,
+                      int training, int act, int64_t count, const double* moments, float* save, void* y,
+                      int64_t ldy, void* stream);
+int dg_swx_bwd_stats(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
+                     int64_t ldx, int N, int HW, int C, int sw_type, int tie, int T, float eps,
+                     const float* mean_w, const float* var_w, const float* gamma, int act,
+                     const float* save, double* bmoments, float* dgamma, float* dbeta, void* workspace,
+                     void* stream);
+int dg_swx_bwd_finish(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
+                      int64_t ldx, int N, int HW, int C, int sw_type, int tie, int act,
+                      const float* mean_w, const float* var_w, const float* save, int64_t count,
+                      const double* bmoments, void* dx, int64_t lddx, int accumulate, float* dmean_w,
+                      float* dvar_w, void* workspace, void* stream);
+int dg_swx_bwd(int dtype, const void* gy, int64_t ldg, const void* y, int64_t ldy, const void* x,
+               int64_t ldx, int N, int HW, int C, int sw_type, int tie, int T, float eps,
+               const float* mean_w, const float* var_w, const float* gamma, int act, const float* save,
+               void* dx, int64_t lddx, int accumulate, float* dgamma, float* dbeta, float* dmean_w,
+               float* dvar_w, void* workspace, void* stream);
 
 /* ---- pooling / resampling ---------------------------------------------------
  * nn.MaxPool2d(2,2) (vgg16_bn features 6,13,23,33) and F.interpolate
