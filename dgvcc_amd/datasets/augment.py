@@ -88,6 +88,91 @@ class RawDenClsBatch:
     st_sizes: torch.Tensor | None = None
 
 
+# per-sample descriptor of dg_resize_crop_u8 / dg_resize_crop_f32 (resize.hip), int32 x 16
+RESIZE_DESC = ("src", "sh", "sw", "oh", "ow", "r0", "c0", "hb", "hw", "kh", "vb", "vw", "kv", "grey", "flip", "tmp")
+
+
+@dataclass
+class RawDenBatch:
+    """A collated DensityMapDataset / JHUDomainDataset training batch before its pixel work (CPU
+    tensors only): per sample the source windows of the image and of the density map that the
+    crop's resampling taps touch, packed end to end, the tap tables (built on the host in float64,
+    datasets/den_dataset.py) and a descriptor [B,16] (RESIZE_DESC); the renormalisation scalars
+    [B]; the point sets; the crop size and the density map's downsample."""
+    img_src: torch.Tensor       # uint8 [pixels, 3]
+    img_desc: torch.Tensor      # int32 [B, 16]
+    img_bounds: torch.Tensor    # int32 [n, 2]: (start in the window, count) per output column / row
+    img_weights: torch.Tensor   # int32, 22 fractional bits
+    map_src: torch.Tensor       # f32 [elements]
+    map_desc: torch.Tensor
+    map_bounds: torch.Tensor
+    map_weights: torch.Tensor   # f32
+    scales: torch.Tensor        # f32 [B]
+    points: tuple
+    crop_size: tuple
+    downsample: int
+
+
+def _resize_args(src, desc, bounds, weights, dev):
+    if desc.device.type != "cpu" or desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != len(RESIZE_DESC):
+        raise ValueError("desc must be a CPU int32 [B, 16] tensor")
+    return (src.to(dev, non_blocking=True).contiguous(), desc.contiguous(),
+            bounds.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous(),
+            weights.to(dev, non_blocking=True).contiguous())
+
+
+def _resize_out(out, shape, dev):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 {shape} tensor on {dev}")
+    return out
+
+
+def resize_crop_u8(src, desc, bounds, weights, crop_size, device, out=None):
+    """[B,3,ch,cw] f32 normalised crops of the PIL-bicubic-resized frames (dg_resize_crop_u8)."""
+    dev = torch.device(device)
+    if src.dtype != torch.uint8 or weights.dtype != torch.int32:
+        raise ValueError("src must be uint8 and weights int32")
+    src, desc, bounds, weights = _resize_args(src, desc, bounds, weights, dev)
+    B, (ch, cw) = desc.shape[0], crop_size
+    out = _resize_out(out, (B, 3, ch, cw), dev)
+    ws = query("dg_resize_crop_workspace", ptr(desc), B, 3)
+    work = torch.empty(ws, dtype=torch.uint8, device=dev)
+    call("dg_resize_crop_u8", ptr(src), src.numel() // 3, ptr(desc), B, ptr(bounds), bounds.numel() // 2,
+         ptr(weights), weights.numel(), ch, cw, ptr(out), ptr(work), ws, stream())
+    return out
+
+
+def resize_crop_f32(src, desc, bounds, weights, scales, crop_size, downsample, device, out=None):
+    """[B,1,ch/ds,cw/ds] f32 block sums of the crops of the resized, renormalised density maps
+    (dg_resize_crop_f32)."""
+    dev = torch.device(device)
+    if src.dtype != torch.float32 or weights.dtype != torch.float32:
+        raise ValueError("src and weights must be float32")
+    src, desc, bounds, weights = _resize_args(src, desc, bounds, weights, dev)
+    B, (ch, cw), ds = desc.shape[0], crop_size, int(downsample)
+    if ds <= 0 or ch % ds or cw % ds:
+        raise ValueError(f"crop {crop_size} is not a multiple of downsample {downsample}")
+    scales = scales.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+    if scales.numel() != B:
+        raise ValueError("one scale per sample")
+    out = _resize_out(out, (B, 1, ch // ds, cw // ds), dev)
+    ws = query("dg_resize_crop_workspace", ptr(desc), B, 4)
+    work = torch.empty(ws, dtype=torch.uint8, device=dev)
+    call("dg_resize_crop_f32", ptr(src), src.numel(), ptr(desc), B, ptr(bounds), bounds.numel() // 2, ptr(weights),
+         weights.numel(), ptr(scales), ch, cw, ds, ptr(out), ptr(work), ws, stream())
+    return out
+
+
+def resize_crop(raw: RawDenBatch, device):
+    """(imgs [B,3,ch,cw], dmaps [B,1,ch/ds,cw/ds]) of a RawDenBatch, all pixel work on `device`."""
+    imgs = resize_crop_u8(raw.img_src, raw.img_desc, raw.img_bounds, raw.img_weights, raw.crop_size, device)
+    dmaps = resize_crop_f32(raw.map_src, raw.map_desc, raw.map_bounds, raw.map_weights, raw.scales, raw.crop_size,
+                            raw.downsample, device)
+    return imgs, dmaps
+
+
 class GtDatas(tuple):
     """The reference's `(points, dmaps, bmaps)` (indexing, [-1] and 3-way unpacking as a plain
     tuple) that also carries the Bayesian-loss batch: `bl = (points_kept, targets, st_sizes)`."""
@@ -146,12 +231,18 @@ def block_map(dmaps: torch.Tensor) -> torch.Tensor:
 
 class DeviceAugment:
     """RawDenClsBatch -> the reference's collated batch (img1, img2, (points, dmaps, bmaps))
-    with all pixel work on `device`."""
+    with all pixel work on `device`; RawDenBatch -> (imgs, imgs, (points, dmaps, <empty tensor>))."""
 
     def __init__(self, device):
         self.device = torch.device(device)
 
-    def __call__(self, raw: RawDenClsBatch):
+    def __call__(self, raw):
+        if isinstance(raw, RawDenBatch):
+            # one view and no block map (den_dataset.py:16-21 collates `images, (points, dmaps)`):
+            # the view stands in both image slots, an empty tensor in the block map's
+            imgs, dmaps = resize_crop(raw, self.device)
+            points = tuple(p.to(self.device) for p in raw.points)
+            return imgs, imgs, (points, dmaps, torch.empty(0, device=self.device))
         imgs = raw.imgs.to(self.device, non_blocking=True)
         params = raw.params.to(device=self.device, dtype=torch.float32).contiguous()
         img1, img2 = augment_den_cls(imgs, params)
@@ -166,6 +257,7 @@ class DeviceAugment:
         return img1, img2, GtDatas(gt_datas, bl)
 
 
-__all__ = ["AUG_PARAMS", "RawDenClsBatch", "DeviceAugment", "GtDatas", "bl_batch", "augment_den_cls", "block_map", "draw_more_transform",
+__all__ = ["AUG_PARAMS", "RESIZE_DESC", "RawDenClsBatch", "RawDenBatch", "DeviceAugment", "resize_crop", "resize_crop_u8",
+           "resize_crop_f32", "GtDatas", "bl_batch", "augment_den_cls", "block_map", "draw_more_transform",
            "new_record", "hue_shift", "gaussian_weights"]
 _ = K  # the kernels module loads the library (fails loudly when it is missing)

@@ -33,6 +33,7 @@ def _load_array(path: str) -> np.ndarray:
 
 class DenClsDataset(torch.utils.data.Dataset):
     """reference datasets/den_cls_dataset.py:16-186 (constructor arguments as the reference)."""
+    dmap_suffix = "_dmap"  # density map beside the points file: <name><dmap_suffix>.npy
 
     def __init__(self, root, crop_size, downsample, method, is_grey=False, unit_size=0, pre_resize=1,
                  roi_map_path=None, gt_dir=None, gen_root=None, bl_targets=False):
@@ -101,7 +102,7 @@ class DenClsDataset(torch.utils.data.Dataset):
             basename = basename[:-2]
             gt_fn = os.path.join(self.root, "train", basename + ".npy")
         if self.gt_dir is None:
-            dmap_fn = gt_fn.replace(basename, basename + "_dmap")
+            dmap_fn = gt_fn.replace(basename, basename + self.dmap_suffix)
         else:
             dmap_fn = os.path.join(self.gt_dir, basename + ".npy")
         return basename, gt_fn, dmap_fn

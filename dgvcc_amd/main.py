@@ -12,8 +12,9 @@ implementations behind them:
 * losses: 'mse' -> the fused HIP MSELoss, 'bl' -> the fused Bayesian loss (its train set then
   also delivers the unfiltered annotations; the per-point targets are computed on the GPU);
 * datasets: 'den_cls' and 'jhu_domain_cls' (every shipped config's train/val/test set)
-  with the pixel augmentation on the GPU; the other reference datasets ('den', 'bay',
-  'jhu_domain') are not on the hot path (SURVEY.md §8) and raise;
+  with the pixel augmentation on the GPU; 'den' and 'jhu_domain' (the baselines' train sets:
+  one view, a random rescale per sample) with the resize, crop, block sum and flip on the GPU
+  (resize.hip; DGTrainer mode 'simple'); 'bay' is not on the hot path (SURVEY.md §8) and raises;
 * optimizer 'adamw' -> the fused HIP AdamW (torch.optim.AdamW semantics, works with
   torch's schedulers including OneCycleLR's beta cycling); 'sgd'/'adam' -> torch's.
 
@@ -66,12 +67,16 @@ def get_loss(name, params):
 
 
 def get_dataset(name, params, method):
-    from .datasets import DenClsDataset, JHUDomainClsDataset
+    from .datasets import DenClsDataset, DensityMapDataset, JHUDomainClsDataset, JHUDomainDataset
     if name == "den_cls":
         return DenClsDataset(method=method, **params), DenClsDataset.collate
     if name == "jhu_domain_cls":
         return JHUDomainClsDataset(method=method, **params), JHUDomainClsDataset.collate
-    if name in ("den", "bay", "jhu_domain"):
+    if name == "den":  # main_base.py's train sets: one view, random rescale on the device
+        return DensityMapDataset(method=method, **params), DensityMapDataset.collate
+    if name == "jhu_domain":
+        return JHUDomainDataset(method=method, **params), JHUDomainDataset.collate
+    if name == "bay":
         raise NotImplementedError(f"dataset '{name}' is outside the ported hot path (SURVEY.md §8)")
     raise ValueError(f"Unknown dataset: {name}")
 

@@ -124,14 +124,20 @@ class DGTrainer(Trainer):
         return cnt
 
     def prepare_batch(self, batch):
-        """A `DenClsDataset.collate` RawDenClsBatch -> the reference's batch layout, with the
-        pixel augmentation run on this trainer's device; reference-layout batches pass through."""
-        from ..datasets.augment import DeviceAugment, RawDenClsBatch
-        if isinstance(batch, RawDenClsBatch):
+        """A `DenClsDataset.collate` RawDenClsBatch or a `DensityMapDataset.collate` RawDenBatch ->
+        the reference's batch layout, with the pixel work run on this trainer's device;
+        reference-layout batches pass through."""
+        from ..datasets.augment import DeviceAugment, RawDenBatch, RawDenClsBatch
+        if isinstance(batch, (RawDenClsBatch, RawDenBatch)):
             return DeviceAugment(self.device)(batch)
         return batch
 
     def train_step(self, model, loss, optimizer, batch, epoch):
+        from ..datasets.augment import RawDenBatch
+        if isinstance(batch, RawDenBatch) and self.mode != "simple":
+            # one view, no block map: nothing for the two-view / cls modes to train on
+            raise ValueError(f"a DensityMapDataset / JHUDomainDataset batch trains in mode 'simple' only, "
+                             f"not in mode '{self.mode}'")
         imgs1, imgs2, gt_datas = self.prepare_batch(batch)
         imgs1 = imgs1.to(self.device, non_blocking=True)
         imgs2 = imgs2.to(self.device, non_blocking=True)

@@ -647,6 +647,31 @@ int dg_augment_den_cls(const unsigned char* imgs, int B, int H, int W, const flo
                        float* img1, float* img2, void* workspace, int64_t ws_bytes, void* stream);
 int dg_block_map(const float* dmap, int B, int h, int w, float* bmap, void* stream);
 
+/* ---- device-side random rescale (DensityMapDataset / JHUDomainDataset, datasets/den_dataset.py:65-122)
+ * Separable resampling of a batch of source windows of different sizes straight into the crop
+ * (resize.hip).  src: the packed windows (uint8 RGB pixels, or f32 elements), src_px pixels in all.
+ * desc: HOST memory, [B][16] int32 per sample: window offset (pixels), window rows, columns; rows,
+ * columns of the crop inside the resized frame and the crop row, column of the first; horizontal
+ * taps: first (start, count) pair in bounds, first weight in weights, weights per output; the same
+ * three for the vertical taps; grey; flip; one word the library fills.  bounds: [n_bounds][2] int32
+ * (start relative to the window); weights: normalised, int32 with 22 fractional bits (u8) or f32.
+ * The host builds the tables in float64 (dgvcc_amd/datasets/den_dataset.py); the kernels do no
+ * filter maths.  Horizontal pass, then vertical pass; no atomics, bit-identical from run to run.
+ * dg_resize_crop_u8: PIL's 8-bit arithmetic (seed 1 << 21, >> 22, clip, uint8 intermediate), grey
+ * before the resize, pixel 0 in the padding, hflip, ToTensor + Normalize(0.5, 0.5):
+ * out [B][3][ch][cw] f32, bit-identical to PIL resize -> pad -> crop -> hflip -> transform.
+ * dg_resize_crop_f32: f32 accumulation, times scales[b], zero padding, ds x ds block sum, hflip:
+ * out [B][1][ch/ds][cw/ds] f32.  At most 48 taps per output, ds <= 16.
+ * workspace: dg_resize_crop_workspace(desc, B, 3 | 4) bytes. */
+int64_t dg_resize_crop_workspace(const int* desc, int B, int px_bytes);
+int dg_resize_crop_u8(const unsigned char* src, int64_t src_px, const int* desc, int B,
+                      const int* bounds, int64_t n_bounds, const int* weights, int64_t n_weights,
+                      int ch, int cw, float* out, void* workspace, int64_t ws_bytes, void* stream);
+int dg_resize_crop_f32(const float* src, int64_t src_px, const int* desc, int B, const int* bounds,
+                       int64_t n_bounds, const float* weights, int64_t n_weights,
+                       const float* scales, int ch, int cw, int ds, float* out, void* workspace,
+                       int64_t ws_bytes, void* stream);
+
 /* ---- density head: 1x1 conv C->1 (+ReLU) --------------------------------------
  * den_head (models/models.py:60-62) / cls_head tail (models/models.py:241-242). */
 int dg_head_fwd(int dtype, const void* x, int64_t ldx, int M, int C, const float* w,
