@@ -751,6 +751,7 @@ __global__ __launch_bounds__(SNT) void bn_part_finalize(const float* __restrict_
   double n = 0.0, s = 0.0;
   for (int b = tid; b < nblk; b += SNT) {
     const double nb = part[b * row + c];
+    if (nb == 0.0) continue;  // an empty row's mean is not read (0 * NaN)
     n += nb;
     s += nb * part[b * row + C + c];
   }
